@@ -15,6 +15,15 @@ hyper-parameter perturbation.  Data: a fixed synthetic device batch per member
 Hyper-parameters are sampled from the reference search space with a fixed seed;
 ``batch_size`` is pinned to 128 for every member so per-step work is identical
 across runs (the search space samples 65..255).
+
+A plain run sets up, warms up, times ``--steps`` steps and prints one JSON result line (``ms_per_step`` = the
+milliseconds one timed step took); ``--dump-outputs DIR`` also writes the last timed step's losses, the
+members' BN statistics and the norm of their weights as ``DIR/<name>.npy``.  With that
+option the last timed step starts from the seeded start condition (weights, hyper-parameters, step counts), not
+from wherever the steps before it led -- float atomics make that point differ from run to run -- so the same
+arguments give the same arrays and two builds can be compared array by array (``dump_outputs`` below).
+``--full`` is where anything beyond the headline figure belongs: today the members' single weights and the
+update's norm in the dump, which do differ between runs.
 """
 
 from __future__ import annotations
@@ -63,6 +72,18 @@ def parse():
     p.add_argument("--batch_sizes", default=None,
                    help="with --ragged: comma-separated per-member batch sizes (e.g. a PBT round's mix from "
                         "metrics.jsonl 'batch_sizes') instead of the sampled ones")
+    p.add_argument("--dump-outputs", dest="dump_outputs", default=None, metavar="DIR",
+                   help="after the timed steps, write what the last timed step left a caller with as DIR/<name>.npy "
+                        ": the per-member losses it returned (float32), the members' BN moving statistics after it "
+                        "(float32) and the L2 norm of their weights (float64); at most "
+                        "64 MB in all. That step then starts from the seeded start condition, so runs with the same "
+                        "arguments write the same arrays")
+    p.add_argument("--full", action="store_true",
+                   help="also do whatever the benchmark measures or checks beyond its headline figure; a plain run "
+                        "only sets up, warms up, times --steps steps and prints the result line. Today: with "
+                        "--dump-outputs also write the members' weights (a fixed, seeded column sample of larger "
+                        "ones) and the norm of the step's update, which differ between runs of one build by more "
+                        "than rounding")
     a = p.parse_args()
     if a.resnet_size is None:
         a.resnet_size = 50 if a.model == "imagenet" else 56
@@ -71,6 +92,49 @@ def parse():
     if a.exploit_offset is None:
         a.exploit_offset = (a.exploit_every or 0) // 2
     return a
+
+
+DUMP_BYTES = 60 << 20  # budget of --dump-outputs (the limit is 64 MB in all; the rest covers the .npy headers)
+
+
+def dump_outputs(out_dir, losses, params, running, params_before, rank, world, full=False):
+    """``--dump-outputs``: the last timed step's results as ``.npy`` files -- ``losses`` [members] (float32), the
+    value ``train_step`` returned, and of the state it left behind ``running`` [members, R] (float32, BN moving
+    statistics) and ``params_norm`` [members] (float64: the L2 norm of each member's weights after the step).
+
+    The weights themselves (``params`` [members, P], float32) and the norm of the step's change to them
+    (``update_norm`` [members], float64) are written only with ``--full``: they are not the same from run to run.
+    The release kernels sum with float atomics, the bf16 layers re-round that difference on the way up and down the
+    network, and the sampled learning rates (up to 2.5; Adam's first update is +-lr by the gradient's sign) scale
+    what arrives.  Measured on an MI355X between runs of one build (ResNet-56, pop 8): single weights differ by up to
+    0.44 relative L2 per member (Adam, lr 0.1) and ``update_norm`` by up to 1.2 %, while ``losses`` and
+    ``params_norm`` agree to 6e-4 and ``running`` to 7e-6.  Weights beyond the byte budget are cut to a fixed,
+    seeded sample of columns (the same columns for every member and every run; their indices go to
+    ``params_columns``).  With more than one rank every rank writes its own members' rows as
+    ``<name>_rank<r>.npy``."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    n, P = params.shape
+    arrays = {"losses": losses.detach().float().reshape(-1).cpu().numpy(),
+              "running": running.float().cpu().numpy(),
+              "params_norm": params.double().norm(dim=1).cpu().numpy()}
+    if full:
+        arrays["update_norm"] = (params.double() - params_before.double()).norm(dim=1).cpu().numpy()
+    left = DUMP_BYTES - sum(a.nbytes for a in arrays.values())
+    if not full:
+        pass
+    elif 4 * n * P > left:
+        cols = max(1, left // (4 * n + 8))  # a column costs one float32 per member + its float64 index
+        pick = np.sort(np.random.RandomState(0).choice(P, size=cols, replace=False))
+        sel = torch.from_numpy(pick).to(params.device)
+        arrays["params"] = params.index_select(1, sel).float().cpu().numpy()
+        arrays["params_columns"] = pick.astype(np.float64)
+    else:
+        arrays["params"] = params.float().cpu().numpy()
+    suffix = "" if world == 1 else "_rank%d" % rank
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), np.ascontiguousarray(a))
 
 
 def main():
@@ -138,6 +202,29 @@ def main():
         bt = batches if not args.ragged else [ds.batch_slice(int(m.hparams["batch_size"])) for m in members]
         images_done[0] += sum(int(b[1].shape[0]) for b in bt)
         return eng.train_step(slots, bt, hp, lrs)
+
+    # --dump-outputs: the release kernels sum with float atomics, so a run's weights after many training steps (and
+    # with them the exploit plans and the explored hyper-parameters) are not the same from run to run.  What is
+    # written must be, so the LAST timed step starts from the seeded start condition kept here (state rows,
+    # hyper-parameters, step counts: the same in every run) and its results are copied on the device as soon as it
+    # is queued, before a later exploit copy can touch them.  Two device copies of the members' rows inside the
+    # timed region, in runs with this option only.
+    slot_idx = torch.tensor(slots, device=eng.state.device, dtype=torch.long)
+    start = dumped = None
+    if args.dump_outputs:
+        import copy
+        start = (eng.state.index_select(0, slot_idx), [copy.deepcopy(m.hparams) for m in members],
+                 [eng.host_step[s] for s in slots])
+
+    def restore_start():
+        eng.state.index_copy_(0, slot_idx, start[0])
+        for m, hp, st in zip(members, start[1], start[2]):
+            m.hparams = copy.deepcopy(hp)
+            m.on_state_imported(st)
+
+    def last_step_results(losses):
+        rows = eng.state.index_select(0, slot_idx)
+        return losses.detach().clone(), rows[:, :eng.P], rows[:, 3 * eng.Pp:3 * eng.Pp + eng.R]
 
     exploits = [0]
     exploit_s = []  # host wall time of each timed exploit/explore cycle (gather + plan + copy + perturb)
@@ -208,7 +295,11 @@ def main():
     pending = []  # (due step, readback) of started exploit cycles
     lag = max(1, args.exploit_lag)
     for k in range(args.steps):
+        if start is not None and k == args.steps - 1:
+            restore_start()
         losses = step()
+        if start is not None and k == args.steps - 1:
+            dumped = last_step_results(losses)
         while pending and pending[0][0] <= k:
             exploit_cycle(pending.pop(0)[1])  # overlaps the steps queued since its readback
         # exploit points sit mid-interval (steps every/2, every/2 + every, ..) rather than on the last step, so
@@ -225,6 +316,8 @@ def main():
     # images trained in the timed steps, summed over ranks (ragged: each member's own, changing batch size)
     images = sum(comm.allgather(images_done[0]))
     value = images / dt_max
+    if dumped is not None:
+        dump_outputs(args.dump_outputs, *dumped, start[0][:, :eng.P], rank, world, full=args.full)
     if rank == 0:
         flops = members[0].arch.flops_per_image() * 3.0 * images / dt_max
         metric = BASELINE_METRIC if args.model == "resnet" and args.resnet_size == 56 and args.resnet_version == 2 else \

@@ -4,7 +4,8 @@ The reference ships TF 1.8 tensor-bundle checkpoints + ``results.json`` for a BN
 layer and every ResNet block variant (v1/v2 x building/bottleneck x projection,
 batch 32, width 8, 4 channels) under
 ``resnet/official/utils/testing/reference_data`` (produced by the
-upstream block test, which the reference tree does not contain).  Each
+upstream block test, which the reference tree does not contain); data-only
+copies are kept under ``tests/golden/reference_data``.  Each
 checkpoint holds the block's weights AND its input tensor; ``results.json`` is
 ``[input shape..., first, last, sum, output shape..., first, last, sum]`` of the
 NHWC tensors.  The files are read with the pure-Python bundle parser
@@ -22,8 +23,8 @@ import torch
 from distributedtf_amd.models import resnet
 from distributedtf_amd.utils.tf_bundle import load_bundle
 
-ROOT = "/root/reference/resnet/official/utils/testing/reference_data"
-pytestmark = pytest.mark.skipif(not os.path.isdir(ROOT), reason="reference fixtures not present")
+# data-only copies of the reference fixtures (tests/golden/reference_data/README.md)
+ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_data")
 
 BLOCKS = [(b, p, v) for b in (False, True) for p in (False, True) for v in (1, 2)]
 

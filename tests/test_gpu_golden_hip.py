@@ -22,10 +22,9 @@ import torch
 from distributedtf_amd.models import resnet
 from distributedtf_amd.utils.tf_bundle import load_bundle
 
-# data-only copies of the reference fixtures (tests/fixtures/reference_resnet/README.md): the GPU box has no
-# /root/reference
-ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "fixtures", "reference_resnet")
-pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not os.path.isdir(ROOT), reason="fixtures not present")]
+# data-only copies of the reference fixtures (tests/golden/reference_data/README.md)
+ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_data", "resnet")
+pytestmark = pytest.mark.gpu
 
 BLOCKS = [(b, p, v) for b in (False, True) for p in (False, True) for v in (1, 2)]
 

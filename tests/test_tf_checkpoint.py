@@ -10,8 +10,10 @@ import torch
 
 from distributedtf_amd.utils import tf_bundle as tb
 
-REF = "/root/reference/resnet/official/utils/testing/reference_data"
+# data-only copies of the reference fixtures (tests/golden/reference_data/README.md)
+REF = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_data")
 FIXTURES = sorted(glob.glob(os.path.join(REF, "**", "model.ckpt.index"), recursive=True))
+assert len(FIXTURES) == 11, "tests/golden/reference_data is incomplete: %d bundles" % len(FIXTURES)
 
 
 def test_crc32c_vectors():
@@ -21,7 +23,6 @@ def test_crc32c_vectors():
     assert tb.crc32c(data) == tb._crc32c_py(data)
 
 
-@pytest.mark.skipif(not FIXTURES, reason="reference fixtures not mounted")
 @pytest.mark.parametrize("index", FIXTURES, ids=lambda p: os.path.basename(os.path.dirname(p)))
 def test_writer_reproduces_tf_saver_bytes(index, tmp_path):
     prefix = index[:-len(".index")]

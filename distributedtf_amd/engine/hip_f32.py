@@ -27,9 +27,8 @@ from typing import Dict, List
 import torch
 
 from .. import ops
-from ..data.datasets import IndexBatch, batch_len
-from .hip_imagenet import BnFinArgs, _register as _register_cg
-from .hip_resnet import advance_steps, note_step_advanced, run_captured, same_batches, upload_hyper
+from .hip_imagenet import BnFinArgs, _register as _register_cg, xcd_order
+from .hip_step import HipBackend, HipPlan, _log2, _p, same_batches
 
 c_void_p, c_int, c_long = ctypes.c_void_p, ctypes.c_int, ctypes.c_long
 CMAX = 64
@@ -107,37 +106,21 @@ def _register():
     _REGISTERED = True
 
 
-def _p(t):
-    return None if t is None else t.data_ptr()
-
-
-def _xcd_order(items, ng):
-    """XCD-aware work order (engine/hip_imagenet.py xcd_order; DTF_CG_XCD)."""
-    from .hip_imagenet import xcd_order
-    return xcd_order(items, ng)
-
-
-def _log2(n):
-    assert n > 0 and n & (n - 1) == 0, n
-    return n.bit_length() - 1
-
-
 def supports(arch) -> bool:
     cfg = getattr(arch, "cfg", None)
     return (cfg is not None and cfg.image_size == 32 and not cfg.bottleneck and cfg.version in (1, 2)
             and cfg.num_classes <= 64 and cfg.final_size <= 256)
 
 
-class HipResNetF32Backend:
-    name = "hip"
-    accepts_index_batches = False
+class HipResNetF32Backend(HipBackend):
+    _plan_cls = None  # _F32Plan (set below)
+    max_plans = 4
 
     def __init__(self, engine):
         _register()
         if not supports(engine.arch):
             raise ValueError("the fp32 HIP backend runs CIFAR-shape building-block ResNets")
-        self.e = engine
-        self.dev = engine.device
+        super().__init__(engine)
         self.prog = engine.arch.prog
         self.cfg = self.prog.cfg
         cap = engine.capacity
@@ -157,52 +140,12 @@ class HipResNetF32Backend:
         self.ident = torch.zeros(cap, 4, CMAX, dtype=torch.float32, device=self.dev)  # v1 ReLU mask (x > 0)
         self.ident[:, 0].fill_(1.0)
         self.ident[:, 3].fill_(1.0)
-        self._plans: Dict[tuple, "_F32Plan"] = {}
-        self.use_graph = (os.environ.get("DTF_HIP_GRAPH", "1") == "1" and os.environ.get("DTF_DEBUG", "0") != "1")
 
     def on_params_changed(self, slots):
         pass  # the kernels read the fp32 master rows directly
 
     def shadow_weights(self):
         return None
-
-    def plan(self, slots, sizes):
-        key = (tuple(slots), tuple(sizes))
-        p = self._plans.get(key)
-        if p is None:
-            if len(self._plans) > 4:
-                self._plans.clear()
-            p = _F32Plan(self, list(slots), list(sizes))
-            self._plans[key] = p
-        return p
-
-    def train_step(self, slots, batches, hparams, lrs):
-        e = self.e
-        batches = [b.materialize() if isinstance(b, IndexBatch) else b for b in batches]
-        sizes = [batch_len(b) for b in batches]
-        p = self.plan(slots, sizes)
-        upload_hyper(e, slots, hparams, lrs)
-        p.load_batch(batches)
-        run_captured(p)
-        note_step_advanced(e, slots)
-        return p.loss_sel.clone()
-
-    def forward_backward(self, slots, batches):
-        raise RuntimeError("HipResNetF32Backend runs whole steps: use train_step")
-
-    def train_correct(self, slots):
-        return self.correct[torch.as_tensor(list(slots), dtype=torch.long, device=self.dev)]
-
-    def eval_plan(self, slots, m):
-        key = (tuple(slots), int(m))
-        plans = self.__dict__.setdefault("_eval_plans", {})
-        p = plans.get(key)
-        if p is None:
-            if len(plans) >= 4:
-                plans.pop(next(iter(plans)))
-            p = _F32Plan(self, list(slots), [int(m)] * len(slots), eval_mode=True)
-            plans[key] = p
-        return p
 
     @torch.no_grad()
     def infer(self, slot, x):
@@ -212,29 +155,8 @@ class HipResNetF32Backend:
         p.run_eval()
         return p.logits_of(slot)
 
-    @torch.no_grad()
-    def evaluate_population(self, slots, x, y, chunk=None):
-        n = int(x.shape[0])
-        if n == 0 or not slots:
-            return {s: 0.0 for s in slots}
-        chunk = min(n, int(chunk or os.environ.get("DTF_EVAL_CHUNK", "2000")))
-        used = []
-        for i in range(0, n, chunk):
-            m = min(chunk, n - i)
-            p = self.eval_plan(slots, m)
-            if all(p is not q for q in used):
-                p.ev_acc.zero_()
-                used.append(p)
-            p.load_eval(x[i:i + m], y[i:i + m])
-            p.run_eval()
-        correct = used[0].ev_acc[0].clone()
-        for p in used[1:]:
-            correct += p.ev_acc[0]
-        vals = correct.cpu().tolist()
-        return {s: vals[s] / float(n) for s in slots}
 
-
-class _F32Plan:
+class _F32Plan(HipPlan):
     def __init__(self, be: HipResNetF32Backend, slots: List[int], sizes: List[int], eval_mode: bool = False):
         self.be, self.e = be, be.e
         self.eval = bool(eval_mode)
@@ -307,13 +229,6 @@ class _F32Plan:
             self._tmp[key] = t
         return t
 
-    def _add(self, fn, *args):
-        self.launches.append((fn, args))
-
-    def _hold(self, o):
-        self._keep.append(o)
-        return o
-
     def cf(self, bn):
         return self.ev_coef[bn] if self.eval else self.be.coef[0, bn]
 
@@ -374,7 +289,7 @@ class _F32Plan:
             for p0 in range(f * hwo, (f + n) * hwo, tp):
                 for o0 in range(0, a.Co, tc):
                     items.append([s, p0, min(p0 + tp, (f + n) * hwo), o0])
-        items = _xcd_order(items, -(-a.Co // tc))
+        items = xcd_order(items, -(-a.Co // tc))
         work = self._hold(torch.tensor(items, dtype=torch.int32, device=self.be.dev))
         a.work = _p(work)
         self._hold(a)
@@ -395,7 +310,7 @@ class _F32Plan:
             for b0 in range(f * bpi, (f + n) * bpi, chunk):
                 for t in tiles:
                     items.append([s, b0, min(b0 + chunk, (f + n) * bpi), t])
-        items = _xcd_order(items, len(tiles))
+        items = xcd_order(items, len(tiles))
         work = self._hold(torch.tensor(items, dtype=torch.int32, device=self.be.dev))
         a.work = _p(work)
         self._hold(a)
@@ -433,7 +348,7 @@ class _F32Plan:
                 for o0 in range(0, c.cout, tc):
                     for n0 in range(0, K, 64):
                         items.append([s, p0, min(p0 + WG_CHUNK, (f + n) * hwo), o0 | ((n0 // 16) << 16)])
-        items = _xcd_order(items, -(-c.cout // tc) * -(-K // 64))
+        items = xcd_order(items, -(-c.cout // tc) * -(-K // 64))
         work = self._hold(torch.tensor(items, dtype=torch.int32, device=self.be.dev))
         a.work = _p(work)
         self._hold(a)
@@ -667,18 +582,5 @@ class _F32Plan:
     def run_eval(self):
         self._run_eager()
 
-    def _run_eager(self):
-        e = self.e
-        st = ops.stream()
-        for fn, args in self.launches:
-            if fn == "zero":
-                args[0].zero_()
-            elif fn == "optim":
-                e.dp_sync_grads(self.slots)
-                ops.fused_optimizer(e.state, e.grads, e.hyper, e.Pp, e.P, e.n_reg, shadow=None, zero_grads=True)
-            elif fn == "step":
-                advance_steps(e, self.slots_long, self.slots_t, self.be.loss, self.loss_sel)
-            else:
-                err = fn(*args, st)
-                if err != 0:
-                    raise RuntimeError("kernel launch %s failed with %d" % (getattr(fn, "__name__", fn), err))
+
+HipResNetF32Backend._plan_cls = _F32Plan

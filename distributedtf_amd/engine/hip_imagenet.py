@@ -26,8 +26,7 @@ from typing import Dict, List
 import torch
 
 from .. import ops
-from ..data.datasets import IndexBatch, batch_len
-from .hip_resnet import advance_steps, run_captured, note_step_advanced, same_batches, upload_hyper
+from .hip_step import HipBackend, HipPlan, _log2, _p, same_batches
 
 c_void_p, c_int, c_long, c_float = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_float
 CMAX = 2048
@@ -250,24 +249,14 @@ def _register():
     _REGISTERED = True
 
 
-def _p(t):
-    return None if t is None else t.data_ptr()
-
-
-def _log2(n):
-    assert n > 0 and n & (n - 1) == 0, n
-    return n.bit_length() - 1
-
-
-class HipImageNetBackend:
-    name = "hip"
-    accepts_index_batches = False
+class HipImageNetBackend(HipBackend):
     _plan_cls = None  # _ImageNetPlan (set below); the fp32 backend: engine/hip_imagenet_f32.py
+    max_plans = 4
+    eval_chunk_env, eval_chunk = "DTF_EVAL_CHUNK_IMAGENET", 64
 
     def __init__(self, engine):
         _register()
-        self.e = engine
-        self.dev = engine.device
+        super().__init__(engine)
         prog = engine.arch.prog
         cfg = prog.cfg
         if not (cfg.bottleneck and cfg.version in (1, 2) and cfg.first_pool_size == 3 and cfg.first_pool_stride == 2
@@ -324,8 +313,6 @@ class HipImageNetBackend:
             self.ident = torch.zeros(cap, 4, CMAX, dtype=torch.float32, device=self.dev)
             self.ident[:, 0].fill_(1.0)
             self.ident[:, 3].fill_(1.0)
-        self._plans: Dict[tuple, "_ImageNetPlan"] = {}
-        self.use_graph = (os.environ.get("DTF_HIP_GRAPH", "1") == "1" and os.environ.get("DTF_DEBUG", "0") != "1")
 
     def on_params_changed(self, slots):
         slots = list(slots)
@@ -335,46 +322,6 @@ class HipImageNetBackend:
 
     def shadow_weights(self):
         return self.shadow
-
-    def plan(self, slots, sizes):
-        key = (tuple(slots), tuple(sizes))
-        p = self._plans.get(key)
-        if p is None:
-            if len(self._plans) > 4:
-                self._plans.clear()
-            p = self._plan_cls(self, list(slots), list(sizes))
-            self._plans[key] = p
-        return p
-
-    def train_step(self, slots, batches, hparams, lrs):
-        e = self.e
-        batches = [b.materialize() if isinstance(b, IndexBatch) else b for b in batches]
-        sizes = [batch_len(b) for b in batches]
-        p = self.plan(slots, sizes)
-        upload_hyper(e, slots, hparams, lrs)
-        p.load_batch(batches)
-        p.run()
-        note_step_advanced(e, slots)
-        return p.loss_sel.clone()  # gathered inside the step graph
-
-    def forward_backward(self, slots, batches):
-        raise RuntimeError("HipImageNetBackend runs whole steps: use train_step")
-
-    def train_correct(self, slots):
-        """Correct predictions of each member's last training batch (softmax-CE kernel count; device tensor)."""
-        return self.correct[torch.as_tensor(list(slots), dtype=torch.long, device=self.dev)]
-
-    def eval_plan(self, slots, m):
-        """Eval plans live in their own bounded cache: an eval pass never evicts the captured training graph."""
-        key = (tuple(slots), int(m))
-        plans = self.__dict__.setdefault("_eval_plans", {})
-        p = plans.get(key)
-        if p is None:
-            if len(plans) >= 4:
-                plans.pop(next(iter(plans)))  # oldest first
-            p = self._plan_cls(self, list(slots), [int(m)] * len(slots), eval_mode=True)
-            plans[key] = p
-        return p
 
     @torch.no_grad()
     def infer(self, slot, x):
@@ -386,31 +333,8 @@ class HipImageNetBackend:
         b = e.state[slot, self.prog.dense_b_off:self.prog.dense_b_off + self.ncls]
         return p.logits[:, :self.ncls] + b
 
-    @torch.no_grad()
-    def evaluate_population(self, slots, x, y, chunk=None):
-        """Eval accuracy of every member in ``slots``: one population-batched forward per chunk of the eval set
-        (BN with moving statistics, the same convg / GAP / dense kernels as training); one host sync."""
-        n = int(x.shape[0])
-        if n == 0 or not slots:
-            return {s: 0.0 for s in slots}
-        chunk = min(n, int(chunk or os.environ.get("DTF_EVAL_CHUNK_IMAGENET", "64")))
-        used = []
-        for i in range(0, n, chunk):
-            m = min(chunk, n - i)
-            p = self.eval_plan(slots, m)
-            if all(p is not q for q in used):
-                p.ev_acc.zero_()
-                used.append(p)
-            p.load_eval(x[i:i + m], y[i:i + m])
-            p.run_eval()
-        correct = used[0].ev_acc[0].clone()
-        for p in used[1:]:
-            correct += p.ev_acc[0]
-        vals = correct.cpu().tolist()
-        return {s: vals[s] / float(n) for s in slots}
 
-
-class _ImageNetPlan:
+class _ImageNetPlan(HipPlan):
     def __init__(self, be: HipImageNetBackend, slots: List[int], sizes: List[int], eval_mode: bool = False):
         self.be, self.e = be, be.e
         self.eval = bool(eval_mode)
@@ -518,13 +442,6 @@ class _ImageNetPlan:
             t = torch.empty(self.N, hw, hw, c, dtype=self._act_dtype(), device=self.be.dev)
             self._tmp[key] = t
         return t
-
-    def _add(self, fn, *args):
-        self.launches.append((fn, args))
-
-    def _hold(self, obj):
-        self._keep.append(obj)
-        return obj
 
     @staticmethod
     def _xcd_order(items, ng):
@@ -838,6 +755,9 @@ class _ImageNetPlan:
     def gap(self, g, which):
         self._add(ops.lib().dtf_cg_gap, ctypes.byref(g), which, self.N)
 
+    def gemm(self, g):
+        self._add(ops.lib().dtf_gemm_bf16, ctypes.byref(g.args), g.mode, g.nwork)
+
     def dense_head(self, train):
         """Dense layer + softmax CE on the GAP features: the grouped bf16 GEMM (padded to NPAD_CLS classes) per
         member, cg_softmax_ce (bias, loss, correct count, dlogits, dbias); training adds dfeat = dlogits W and
@@ -855,7 +775,7 @@ class _ImageNetPlan:
             wgr.append((f0 * NPAD_CLS, f0 * C, s * e.Pp + prog.dense_w_off, NPAD_CLS, C, n, be.ncls))
         dev = be.dev
         self.g_fwd = GroupedGemm(self.feat, be.dense, self.logits, C, C, NPAD_CLS, fwd, False, False, GEMM_OUT_F32, dev)
-        self._add("gemm", self.g_fwd)
+        self.gemm(self.g_fwd)
         if not train:
             self._add(L.dtf_cg_softmax_ce, _p(self.logits), NPAD_CLS, be.ncls, _p(self.labels), _p(self.img_slot),
                       _p(e.state), e.S, prog.dense_b_off, None, e.Pp, _p(self.cnt), _p(self.ev_loss),
@@ -866,8 +786,8 @@ class _ImageNetPlan:
         self._add(L.dtf_cg_softmax_ce, _p(self.logits), NPAD_CLS, be.ncls, _p(self.labels), _p(self.img_slot),
                   _p(e.state), e.S, prog.dense_b_off, _p(be.acc_grads), e.Pp, _p(self.cnt), _p(be.acc_loss),
                   _p(be.correct), _p(self.dlog), self.N, be.loss_scale)
-        self._add("gemm", self.g_dgr)
-        self._add("gemm", self.g_wgr)
+        self.gemm(self.g_dgr)
+        self.gemm(self.g_wgr)
 
     FOLD1_OK = True  # the fp32 plan (hip_imagenet_f32.py) keeps the materialised relu(BN1(x))
     GFOLD_OK = True  # ... and the standalone block-input gradient apply
@@ -1273,29 +1193,6 @@ class _ImageNetPlan:
             self.x_in[off:off + n].copy_(x.reshape(n, *self.x_in.shape[1:]), non_blocking=True)
             self.labels[off:off + n].copy_(y, non_blocking=True)
             off += n
-
-    def _run_eager(self):
-        e = self.e
-        st = ops.stream()
-        for fn, args in self.launches:
-            if fn == "zero":
-                args[0].zero_()
-            elif fn == "gemm":
-                args[0].launch(st)
-            elif fn == "optim":
-                e.dp_sync_grads(self.slots)  # data-parallel member groups only (no-op otherwise)
-                ops.fused_optimizer(e.state, e.grads, e.hyper, e.Pp, e.P, e.n_reg, shadow=self.be.shadow,
-                                    zero_grads=True, grad_scale=1.0 / self.be.loss_scale)
-            elif fn == "step":
-                # step counters + per-member losses gathered inside the step (graph): a replay leaves one copy
-                advance_steps(e, self.slots_long, self.slots_t, self.be.loss, self.loss_sel)
-            else:
-                err = fn(*args, st)
-                if err != 0:
-                    raise RuntimeError("kernel launch %s failed with %d" % (getattr(fn, "__name__", fn), err))
-
-    def run(self):
-        run_captured(self)
 
 
 HipImageNetBackend._plan_cls = _ImageNetPlan

@@ -22,14 +22,13 @@ the bf16 step does.  The step is captured in one HIP graph per batch composition
 from __future__ import annotations
 
 import ctypes
-import os
 
 import torch
 
 from .. import ops
 from .hip_f32 import F32Args, F32Ew, F32Sum, TP, WG_CHUNK, _register as _register_f32
-from .hip_imagenet import (CMAX, NPAD_CLS, GapArgs, HipImageNetBackend, _ImageNetPlan, _log2,
-                           _register as _register_cg)
+from .hip_imagenet import CMAX, NPAD_CLS, GapArgs, HipImageNetBackend, _ImageNetPlan, _register as _register_cg
+from .hip_step import HipBackend, _log2, _p
 
 c_void_p, c_int, c_long = ctypes.c_void_p, ctypes.c_int, ctypes.c_long
 
@@ -59,10 +58,6 @@ def _register():
     _REGISTERED = True
 
 
-def _p(t):
-    return None if t is None else t.data_ptr()
-
-
 def supports(arch) -> bool:
     cfg = getattr(arch, "cfg", None)
     return (cfg is not None and cfg.bottleneck and cfg.version in (1, 2) and cfg.in_channels == 3
@@ -77,8 +72,7 @@ class HipImageNetF32Backend(HipImageNetBackend):
         _register()
         if not supports(engine.arch):
             raise ValueError("the fp32 HIP ImageNet backend runs the v1 / v2 bottleneck ImageNet configurations")
-        self.e = engine
-        self.dev = engine.device
+        HipBackend.__init__(self, engine)  # (not the bf16 parent's: none of its weight copies are wanted here)
         prog = engine.arch.prog
         self.prog, self.cfg = prog, prog.cfg
         cap = engine.capacity
@@ -105,8 +99,6 @@ class HipImageNetF32Backend(HipImageNetBackend):
         self.ident = torch.zeros(cap, 4, CMAX, dtype=torch.float32, device=self.dev)
         self.ident[:, 0].fill_(1.0)
         self.ident[:, 3].fill_(1.0)
-        self._plans = {}
-        self.use_graph = (os.environ.get("DTF_HIP_GRAPH", "1") == "1" and os.environ.get("DTF_DEBUG", "0") != "1")
 
     def on_params_changed(self, slots):
         pass

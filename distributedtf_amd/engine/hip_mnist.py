@@ -24,15 +24,14 @@ member at once over chunks of the eval set (``evaluate_population``).
 from __future__ import annotations
 
 import ctypes
-import os
-from typing import Dict, List, Sequence
+from typing import List, Sequence
 
 import numpy as np
 import torch
 
 from .. import ops
-from ..data.datasets import IndexBatch, batch_len
-from .hip_resnet import PinnedStager, advance_steps, note_step_advanced, run_captured, same_batches, upload_hyper
+from ..data.datasets import batch_len
+from .hip_step import HipBackend, PinnedStager, _p, advance_steps, run_captured, same_batches
 
 c_void_p, c_int, c_long, c_float = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_float
 
@@ -90,10 +89,6 @@ def _register():
     _REGISTERED = True
 
 
-def _p(t):
-    return None if t is None else t.data_ptr()
-
-
 def dropout_keep_mask(seed: int, counter: int, n_img: int, rate: float, features: int = 1024) -> np.ndarray:
     """Host replica of the head kernel's dropout hash: bool [n_img, features] (True = kept)."""
     from ..data.datasets import _mix32
@@ -143,33 +138,35 @@ class GroupedGemm:
             raise RuntimeError("gemm_bf16 launch failed: %d" % err)
 
 
-class HipMnistBackend:
-    name = "hip"
-    accepts_index_batches = False
+class HipMnistBackend(HipBackend):
+    _plan_cls = None  # _MnistPlan (set below); the fp32 backend: engine/hip_mnist_f32.py
+    eval_chunk = 2500
 
     def __init__(self, engine):
         _register()
-        self.e = engine
-        self.dev = engine.device
-        arch = engine.arch
-        self.offs = {n: arch.offsets[n][0] for n in arch.offsets}
+        self._init_shared(engine)
         for n in ("conv2_w", "dense1_w"):
             assert self.offs[n] % 8 == 0, "bf16 shadow operands must be 16-byte aligned"
         cap = engine.capacity
         self.shadow = torch.zeros(cap, engine.Pp, dtype=torch.bfloat16, device=self.dev)
         self.wd = torch.zeros(cap, 51200, dtype=torch.bfloat16, device=self.dev)
+
+    def _init_shared(self, engine):
+        """What the bf16 and the fp32 backend both hold: parameter offsets, loss / correct rows, dropout rng."""
+        HipBackend.__init__(self, engine)
+        arch = engine.arch
+        self.offs = {n: arch.offsets[n][0] for n in arch.offsets}
+        cap = engine.capacity
         self.loss = torch.zeros(cap, dtype=torch.float32, device=self.dev)
         self.correct = torch.zeros(cap, dtype=torch.float32, device=self.dev)
         self.rng = torch.zeros(2, dtype=torch.int32, device=self.dev)
         self.rng_seed = 0x5EED
         self.rng_counter = 0
         self.drop_rate = float(getattr(arch, "dropout", 0.4))
-        self._plans: Dict[tuple, "_MnistPlan"] = {}
         # training plans also write the head's logits (the "probabilities" hook, reference mnist_model.py:149-151);
         # set before the first step (EngineModel._hooks): the flag is baked into a plan's captured launches
         self.keep_probs = False
         self._last_plan = None
-        self.use_graph = (os.environ.get("DTF_HIP_GRAPH", "1") == "1" and os.environ.get("DTF_DEBUG", "0") != "1")
 
     # engine hooks ----------------------------------------------------------------------------
     def on_params_changed(self, slots):
@@ -190,36 +187,12 @@ class HipMnistBackend:
         self.rng_counter = (self.rng_counter + 1) & 0x7FFFFFFF
         return self.rng_seed, self.rng_counter
 
-    def plan(self, slots, sizes):
-        key = (tuple(slots), tuple(sizes))
-        p = self._plans.get(key)
-        if p is None:
-            if len(self._plans) > 16:
-                self._plans.clear()
-            p = _MnistPlan(self, list(slots), list(sizes))
-            self._plans[key] = p
-        return p
-
     def train_step(self, slots, batches, hparams, lrs):
-        e = self.e
-        batches = [b.materialize() if isinstance(b, IndexBatch) else b for b in batches]
-        sizes = [batch_len(b) for b in batches]
-        p = self.plan(slots, sizes)
-        upload_hyper(e, slots, hparams, lrs)
         self.last_rng = self.next_rng()
         self._upload_rng(self.last_rng)
-        p.load_batch(batches)
-        p.run()
-        self._last_plan = p
-        note_step_advanced(e, slots)
-        return p.loss_sel.clone()  # gathered inside the step graph
-
-    def forward_backward(self, slots, batches):
-        raise RuntimeError("HipMnistBackend runs whole steps: use train_step")
-
-    def train_correct(self, slots):
-        """Correct predictions of each member's last training batch (head kernel count; device tensor)."""
-        return self.correct[torch.as_tensor(list(slots), dtype=torch.long, device=self.dev)]
+        loss = super().train_step(slots, batches, hparams, lrs)
+        self._last_plan = self.plan(slots, [batch_len(b) for b in batches])  # the plan that just ran (cached)
+        return loss
 
     def train_probabilities(self, slots):
         """Softmax of each member's last training batch (with dropout, as the reference's ``softmax_tensor`` in
@@ -236,18 +209,6 @@ class HipMnistBackend:
             out.append(torch.softmax(p.logits[f:f + n], dim=1))
         return out
 
-    def eval_plan(self, slots, m):
-        """Eval plans live in their own bounded cache: an eval pass never evicts the captured training graph."""
-        key = (tuple(slots), int(m))
-        plans = self.__dict__.setdefault("_eval_plans", {})
-        p = plans.get(key)
-        if p is None:
-            if len(plans) >= 4:
-                plans.pop(next(iter(plans)))  # oldest first
-            p = _MnistPlan(self, list(slots), [int(m)] * len(slots), eval_mode=True)
-            plans[key] = p
-        return p
-
     @torch.no_grad()
     def infer(self, slot, x):
         """Eval-mode logits of one member on the HIP forward kernels (dropout off)."""
@@ -256,29 +217,6 @@ class HipMnistBackend:
         p.load_eval(x, torch.zeros(x.shape[0], dtype=torch.int32, device=x.device))
         p.run_eval()
         return logits.clone()
-
-    @torch.no_grad()
-    def evaluate_population(self, slots, x, y, chunk=None):
-        """Eval accuracy of every member in ``slots``: one population-batched forward (conv1, conv2, dense1 grouped
-        GEMM, head without dropout) per chunk of the eval set; one host sync at the end."""
-        n = int(x.shape[0])
-        if n == 0 or not slots:
-            return {s: 0.0 for s in slots}
-        chunk = min(n, int(chunk or os.environ.get("DTF_EVAL_CHUNK", "2500")))
-        used = []
-        for i in range(0, n, chunk):
-            m = min(chunk, n - i)
-            p = self.eval_plan(slots, m)
-            if all(p is not q for q in used):
-                p.ev_acc.zero_()
-                used.append(p)
-            p.load_eval(x[i:i + m], y[i:i + m])
-            p.run_eval()
-        correct = used[0].ev_acc[0].clone()
-        for p in used[1:]:
-            correct += p.ev_acc[0]
-        vals = correct.cpu().tolist()
-        return {s: vals[s] / float(n) for s in slots}
 
 
 class _MnistPlan:
@@ -434,3 +372,6 @@ class _MnistPlan:
 
     def run(self):
         run_captured(self)
+
+
+HipMnistBackend._plan_cls = _MnistPlan

@@ -28,7 +28,6 @@ captured in one HIP graph per batch composition.
 from __future__ import annotations
 
 import ctypes
-import os
 from typing import List
 
 import torch
@@ -36,7 +35,7 @@ import torch
 from .. import ops
 from .hip_f32 import F32Args, TP, WG_CHUNK, _register as _register_f32
 from .hip_mnist import HipMnistBackend, MnistArgs, _register as _register_mnist
-from .hip_resnet import advance_steps, run_captured
+from .hip_step import HipPlan, _p, same_batches
 
 c_void_p, c_int, c_long = ctypes.c_void_p, ctypes.c_int, ctypes.c_long
 
@@ -74,20 +73,13 @@ def _register():
     _REGISTERED = True
 
 
-def _p(t):
-    return None if t is None else t.data_ptr()
-
-
 class HipMnistF32Backend(HipMnistBackend):
     """fp32 MNIST step: the bf16 backend's engine hooks, rng and eval drivers over fp32 plans."""
 
     def __init__(self, engine):
         _register()
         e = engine
-        self.e = e
-        self.dev = e.device
-        arch = e.arch
-        self.offs = {n: arch.offsets[n][0] for n in arch.offsets}
+        self._init_shared(e)
         for n in ("dense1_b", "dense2_w"):
             assert self.offs[n] % 4 == 0, "the head reads float4 rows"
         cap = e.capacity
@@ -96,16 +88,6 @@ class HipMnistF32Backend(HipMnistBackend):
         self.loss_sink = torch.zeros(cap, dtype=torch.float32, device=self.dev) if self.det else None
         self.loss64_sink = torch.zeros(cap, dtype=torch.int64, device=self.dev) if self.det else None
         self.shadow = None
-        self.loss = torch.zeros(cap, dtype=torch.float32, device=self.dev)
-        self.correct = torch.zeros(cap, dtype=torch.float32, device=self.dev)
-        self.rng = torch.zeros(2, dtype=torch.int32, device=self.dev)
-        self.rng_seed = 0x5EED
-        self.rng_counter = 0
-        self.drop_rate = float(getattr(arch, "dropout", 0.4))
-        self._plans = {}
-        self.keep_probs = False
-        self._last_plan = None
-        self.use_graph = (os.environ.get("DTF_HIP_GRAPH", "1") == "1" and os.environ.get("DTF_DEBUG", "0") != "1")
 
     def on_params_changed(self, slots):
         pass  # the kernels read the fp32 master rows directly
@@ -113,29 +95,8 @@ class HipMnistF32Backend(HipMnistBackend):
     def shadow_weights(self):
         return None
 
-    def plan(self, slots, sizes):
-        key = (tuple(slots), tuple(sizes))
-        p = self._plans.get(key)
-        if p is None:
-            if len(self._plans) > 16:
-                self._plans.clear()
-            p = _MnistF32Plan(self, list(slots), list(sizes))
-            self._plans[key] = p
-        return p
 
-    def eval_plan(self, slots, m):
-        key = (tuple(slots), int(m))
-        plans = self.__dict__.setdefault("_eval_plans", {})
-        p = plans.get(key)
-        if p is None:
-            if len(plans) >= 4:
-                plans.pop(next(iter(plans)))
-            p = _MnistF32Plan(self, list(slots), [int(m)] * len(slots), eval_mode=True)
-            plans[key] = p
-        return p
-
-
-class _MnistF32Plan:
+class _MnistF32Plan(HipPlan):
     def __init__(self, be: HipMnistF32Backend, slots: List[int], sizes: List[int], eval_mode: bool = False):
         self.be, self.e = be, be.e
         self.eval = bool(eval_mode)
@@ -193,6 +154,7 @@ class _MnistF32Plan:
             a.logits_out = _p(self.logits)
         # head chunks (img0, nimg, 0, slot): deterministic build -> one workgroup per member
         self.w_head = self._chunks(1 << 30 if be.det else 16)
+        a.work = _p(self.w_head)
         self._build()
 
     # ------------------------------------------------------------------------------------------------ helpers
@@ -203,13 +165,6 @@ class _MnistF32Plan:
             for i in range(0, n, chunk):
                 items.append([f + i, min(chunk, n - i), 0, s])
         return torch.tensor(items, dtype=torch.int32, device=self.be.dev)
-
-    def _add(self, fn, *args):
-        self.launches.append((fn, args))
-
-    def _hold(self, o):
-        self._keep.append(o)
-        return o
 
     def _f32args(self, w_off, Hi, Ci, wci, Ho, Co, k, pad):
         e = self.e
@@ -296,7 +251,7 @@ class _MnistF32Plan:
         self.conv(self.p1, self.h2, o["conv2_w"], 14, 32, 32, 14, 64, 5, 2)
         self.pool(self.h2, self.p2, self.am2, o["conv2_b"], 14, 64)
         self.conv(self.p2, self.z, o["dense1_w"], 7, 64, 64, 1, 1024, 7, 0)
-        self._add("head", None)
+        self._add(ops.lib().dtf_mnist_head, ctypes.byref(self.head_args), self.w_head.shape[0])
 
     def _build(self):
         o, be, e = self.be.offs, self.be, self.e
@@ -334,7 +289,6 @@ class _MnistF32Plan:
         self.labels.view(k, m).copy_(y.reshape(1, m).expand(k, -1))
 
     def load_batch(self, batches):
-        from .hip_resnet import same_batches
         if same_batches(self, batches):
             return
         off = 0
@@ -348,28 +302,5 @@ class _MnistF32Plan:
         assert self.eval
         self._run_eager()
 
-    def run(self):
-        run_captured(self)
 
-    def _run_eager(self):
-        e, be = self.e, self.be
-        st = ops.stream()
-        for fn, args in self.launches:
-            if fn == "zero":
-                args[0].zero_()
-            elif fn == "head":
-                ops.check(ops.lib().dtf_mnist_head(ctypes.byref(self._head_with_work()), self.w_head.shape[0], st),
-                          "mnist_head (fp32)")
-            elif fn == "optim":
-                e.dp_sync_grads(self.slots)
-                ops.fused_optimizer(e.state, e.grads, e.hyper, e.Pp, e.P, e.n_reg, shadow=None, zero_grads=True)
-            elif fn == "step":
-                advance_steps(e, self.slots_long, self.slots_t, be.loss, self.loss_sel)
-            else:
-                err = fn(*args, st)
-                if err != 0:
-                    raise RuntimeError("kernel launch %s failed with %d" % (getattr(fn, "__name__", fn), err))
-
-    def _head_with_work(self):
-        self.head_args.work = _p(self.w_head)
-        return self.head_args
+HipMnistF32Backend._plan_cls = _MnistF32Plan

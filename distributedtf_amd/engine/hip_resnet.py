@@ -28,14 +28,15 @@ from __future__ import annotations
 
 import ctypes
 import os
-import weakref
-from typing import Dict, List, Sequence, Tuple
+from typing import List, Sequence, Tuple
 
 import torch
 
 from .. import ops
 from ..data.datasets import IndexBatch, batch_len
 from ..models.resnet import BN_EPS
+from .hip_step import (HipBackend, LossRing, PinnedStager, _LIVE_GRAPH_PLANS, _p, advance_steps,  # noqa: F401
+                       graph_state, note_step_advanced, release_graphs, run_captured, same_batches, upload_hyper)
 
 def _nrep() -> int:
     """BN statistic replicas, as compiled into the loaded library (common.h DTF_NREP; 64 in the deterministic
@@ -314,10 +315,6 @@ def _cpad_fwd(c: int) -> int:
     return _CPAD_FWD[c]
 
 
-def _p(t):
-    return None if t is None else t.data_ptr()
-
-
 def _check(err, what):
     if err != 0:
         raise RuntimeError("%s: launch error %d (unsupported shape or HIP error)" % (what, err))
@@ -380,192 +377,14 @@ class _Layout:
         self.bn_table = [[b.run_off, b.c, self.bn_hw[b.idx], b.idx, b.gamma_off, b.beta_off, 0, 0] for b in prog.bns]
 
 
-def upload_hyper(e, slots, hparams, lrs):
-    """Per-member optimizer hyper rows -> device table, skipped when only the step counter moved (the lr
-    schedule is piecewise constant).  The captured step advances the table's step column on the device
-    (``advance_steps``) and ``e._hyper_dev`` mirrors what the device holds, so a skip is exact -- also after
-    an exploit import changes a member's step."""
-    from .optim import H_STEP, hyper_row
-    rows = [(s, hyper_row(hp, lr, e.host_step[s] + 1, True)) for s, hp, lr in zip(slots, hparams, lrs)]
-    dev = getattr(e, "_hyper_dev", None)
-    if dev is not None and dev.get("slots") == tuple(slots) and all(dev.get(s) == r for s, r in rows):
-        return
-    hy = torch.zeros(e.capacity, 8, dtype=torch.float32)
-    for s, r in rows:
-        hy[s] = torch.tensor(r)
-    e.hyper.copy_(hy.pin_memory() if e.device.type == "cuda" else hy, non_blocking=True)
-    e._hyper_dev = {s: list(r) for s, r in rows}
-    e._hyper_dev["slots"] = tuple(slots)
-
-
-class PinnedStager:
-    """Small per-step host->device uploads through one pinned staging buffer.
-
-    A pageable ``non_blocking`` copy is staged synchronously and waits for the stream to drain, so the host
-    cannot queue step k+1 while step k runs.  Here the host waits only for the previous upload from this stager
-    (issued at the start of the previous step) before overwriting the staging buffer."""
-
-    def __init__(self, n, dtype):
-        self.host = torch.empty(n, dtype=dtype).pin_memory() if torch.cuda.is_available() else None
-        self.evt = None
-
-    def upload(self, dst, values):
-        if dst.device.type != "cuda" or self.host is None:
-            dst.copy_(torch.tensor(list(values), dtype=dst.dtype))
-            return
-        if self.evt is None:
-            self.evt = torch.cuda.Event()
-        else:
-            self.evt.synchronize()
-        for i, v in enumerate(values):
-            self.host[i] = v
-        dst.copy_(self.host[:len(values)], non_blocking=True)
-        self.evt.record()
-
-
-def note_step_advanced(e, slots):
-    """Host mirror of ``advance_steps`` (call once per executed step)."""
-    from .optim import H_STEP
-    dev = getattr(e, "_hyper_dev", None)
-    if dev is not None:
-        for s in slots:
-            if s in dev:
-                dev[s][H_STEP] += 1.0
-
-
-def advance_steps(e, slots_long, slots_i32=None, loss=None, loss_sel=None, ring=None):
-    """Inside the captured step: per-member step counters (state column + hyper table) += 1 and, given
-    ``loss``/``loss_sel``, the per-member losses gathered in slot-list order (one kernel when the int32 slot list is
-    given).  ``ring`` = (rows [R, n] fp32, index int32 [1]): the losses go to the ring's next row instead of
-    ``loss_sel`` (LossRing)."""
-    from .optim import H_STEP
-    if slots_i32 is not None and e.device.type == "cuda":
-        rb, ri = (ring.rows, ring.idx) if ring is not None else (None, None)
-        ops.check(ops.lib().dtf_step_end(_p(e.state), e.S, 3 * e.Pp + e.R, _p(e.hyper), H_STEP, _p(slots_i32),
-                                         slots_i32.numel(), _p(loss), _p(loss_sel) if ring is None else None,
-                                         _p(rb), _p(ri), rb.shape[0] if rb is not None else 0, ops.stream()),
-                  "step_end")
-        return
-    one = torch.ones(slots_long.numel(), device=e.device)
-    e.step_col().index_add_(0, slots_long, one)
-    e.hyper[:, H_STEP].index_add_(0, slots_long, one)
-    if loss_sel is not None:
-        torch.index_select(loss, 0, slots_long, out=loss_sel)
-
-
-class LossRing:
-    """Per-step member losses without a per-step copy: the captured step's step_end kernel writes each replay's
-    losses into the next row of a [rows, n] device ring (the row index lives on the device), and the host hands out
-    a VIEW of that row.  A view stays valid for ``rows`` later steps; engine_model._train_cycle clones a member's
-    last loss when the member leaves the active set (before its view can be overwritten)."""
-
-    ROWS = 4096
-
-    def __init__(self, n, device):
-        self.rows = torch.zeros(self.ROWS, n, dtype=torch.float32, device=device)
-        self.idx = torch.zeros(1, dtype=torch.int32, device=device)
-        self.k = 0  # host mirror of idx: steps executed
-
-    def advance(self):
-        self.k += 1
-
-    def last(self):
-        assert self.k > 0
-        return self.rows[(self.k - 1) % self.ROWS]
-
-
-_LIVE_GRAPH_PLANS = weakref.WeakSet()  # plans holding a captured step graph (released before RCCL teardown)
-
-
-def release_graphs() -> int:
-    """Drop every captured step graph (they are re-captured on the next step).  A graph that recorded an RCCL
-    collective keeps that communicator busy: ``destroy_process_group`` then blocks forever (measured with the
-    data-parallel step on the GPU box), so ``parallel.comm.shutdown_distributed`` calls this first."""
-    n = 0
-    for plan in list(_LIVE_GRAPH_PLANS):
-        if plan.graph is not None:
-            plan.graph = None
-            n += 1
-    _LIVE_GRAPH_PLANS.clear()
-    return n
-
-
-def run_captured(plan) -> None:
-    """Run one step of ``plan``: the first call executes it eagerly (allocator / lazy init warm-up) and then
-    captures the launch list into a HIP graph; later calls replay the graph.  A data-parallel step captures its
-    RCCL gradient all-reduce with the rest of the step; if this RCCL build refuses a collective inside a capture,
-    the plan falls back to eager launches (the warm-up already ran this step)."""
-    be = plan.be
-    if be.use_graph and plan.graph is None and not getattr(plan, "_no_graph", False):
-        plan._run_eager()
-        torch.cuda.synchronize()
-        g = torch.cuda.CUDAGraph()
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
-        ok = False
-        try:
-            with torch.cuda.stream(s):
-                g.capture_begin(capture_error_mode="thread_local")
-                try:
-                    plan._run_eager()
-                finally:
-                    g.capture_end()
-            ok = True
-        except RuntimeError as err:
-            if plan.e.dp is None:
-                raise
-            import sys
-            import warnings
-            msg = "step graph capture with the data-parallel all-reduce failed (%s): eager launches" % err
-            warnings.warn(msg)
-            print("DTF WARNING: " + msg, file=sys.stderr, flush=True)
-            torch.cuda.synchronize()
-            plan._no_graph = True
-            be.graph_fallbacks = getattr(be, "graph_fallbacks", 0) + 1
-        torch.cuda.current_stream().wait_stream(s)
-        if ok:
-            plan.graph = g
-            be.graphs_captured = getattr(be, "graphs_captured", 0) + 1
-            _LIVE_GRAPH_PLANS.add(plan)
-        return
-    if plan.graph is not None:
-        plan.graph.replay()
-    else:
-        plan._run_eager()
-
-
-def graph_state(be):
-    """How a HIP backend's steps run: "captured" (HIP-graph replay), "eager_fallback" (a data-parallel capture was
-    refused and at least one plan runs its launches eagerly -- slow, recorded in the bench JSON and metrics.jsonl),
-    "disabled" (DTF_HIP_GRAPH=0 / debug), "none" (nothing captured yet), or None (not a HIP backend)."""
-    if not hasattr(be, "use_graph"):
-        return None
-    if not be.use_graph:
-        return "disabled"
-    if getattr(be, "graph_fallbacks", 0):
-        return "eager_fallback"
-    return "captured" if getattr(be, "graphs_captured", 0) else "none"
-
-
-def same_batches(plan, batches) -> bool:
-    """True if ``batches`` are the very (x, y) storages staged last step and unmodified since (tensor version
-    counters); a reference to them is held so their memory cannot be recycled into a different batch."""
-    key = tuple((x.data_ptr(), x.shape, x.stride(), x._version, y.data_ptr(), y.shape, y._version)
-                for x, y in batches)
-    if getattr(plan, "_batch_key", None) == key:
-        return True
-    plan._batch_key = key
-    plan._batch_ref = list(batches)
-    return False
-
-
-class HipResNetBackend:
-    name = "hip"
+class HipResNetBackend(HipBackend):
+    accepts_index_batches = True
+    _plan_cls = None  # _StepPlan (set below)
+    max_eval_plans = 9
 
     def __init__(self, engine):
         _register()
-        self.e = engine
-        self.dev = engine.device
+        super().__init__(engine)
         self.L = _Layout(engine)
         cap = engine.capacity
         self.wf = torch.zeros(cap, self.L.wtot, dtype=ops.act_dtype(), device=self.dev)
@@ -591,8 +410,6 @@ class HipResNetBackend:
         self.bn_table_t = torch.tensor(self.L.bn_table, dtype=torch.int32, device=self.dev)
         self.loss = self.zbuf[nst:nst + cap]
         self.correct = self.zbuf[nst + cap:]
-        self._plans: Dict[tuple, "_StepPlan"] = {}
-        self.use_graph = (os.environ.get("DTF_HIP_GRAPH", "1") == "1" and os.environ.get("DTF_DEBUG", "0") != "1")
 
     # --- engine hooks --------------------------------------------------------------
     def persist_failures(self) -> int:
@@ -614,8 +431,6 @@ class HipResNetBackend:
         return self.stats[1, bn]
 
     # --- plans ------------------------------------------------------------------------
-    accepts_index_batches = True
-
     def _elastic_cap(self, sizes, force=False):
         """Per-member capacity of an elastic plan for these batch sizes, or None for an exact plan.  Mixed batch
         sizes (PBT samples and perturbs them, constants.py:91-93) run on one capacity-keyed plan whose work tables
@@ -646,7 +461,7 @@ class HipResNetBackend:
         key = (tuple(slots), ("elastic", cap) if cap else tuple(sizes), src_id)
         p = self._plans.get(key)
         if p is None:
-            if len(self._plans) > 16:
+            if len(self._plans) > self.max_plans:
                 self._plans.clear()
             p = _StepPlan(self, list(slots), list(sizes), src, elastic_cap=cap)
             self._plans[key] = p
@@ -689,13 +504,6 @@ class HipResNetBackend:
             return p.loss_view()[p.slot_index(slots)]
         return p.loss_view()
 
-    def forward_backward(self, slots, batches):
-        raise RuntimeError("HipResNetBackend runs whole steps: use train_step")
-
-    def train_correct(self, slots):
-        """Correct predictions of each member's last training batch (head kernel count; device tensor)."""
-        return self.correct[torch.as_tensor(list(slots), dtype=torch.long, device=self.dev)]
-
     @torch.no_grad()
     def infer(self, slot, x):
         """Eval-mode logits of one member on the HIP forward kernels (moving BN statistics)."""
@@ -704,40 +512,6 @@ class HipResNetBackend:
         p.load_eval(x, torch.zeros(x.shape[0], dtype=torch.int32, device=x.device))
         p.run_eval()
         return logits.clone()
-
-    def eval_plan(self, slots, m):
-        key = (tuple(slots), int(m))
-        plans = self.__dict__.setdefault("_eval_plans", {})
-        p = plans.get(key)
-        if p is None:
-            if len(plans) > 8:
-                plans.clear()
-            p = _StepPlan(self, list(slots), [int(m)] * len(slots), None, eval_mode=True)
-            plans[key] = p
-        return p
-
-    @torch.no_grad()
-    def evaluate_population(self, slots, x, y, chunk=None):
-        """Eval accuracy of every member in ``slots`` on (x, y) in one population-batched forward per chunk of
-        ``chunk`` images (all members see the same chunk); one host sync at the end."""
-        n = int(x.shape[0])
-        if n == 0 or not slots:
-            return {s: 0.0 for s in slots}
-        chunk = min(n, int(chunk or os.environ.get("DTF_EVAL_CHUNK", "2000")))
-        used = []
-        for i in range(0, n, chunk):
-            m = min(chunk, n - i)
-            p = self.eval_plan(slots, m)
-            if all(p is not q for q in used):
-                p.ev_acc.zero_()
-                used.append(p)
-            p.load_eval(x[i:i + m], y[i:i + m])
-            p.run_eval()
-        correct = used[0].ev_acc[0].clone()
-        for p in used[1:]:
-            correct += p.ev_acc[0]
-        vals = correct.cpu().tolist()
-        return {s: vals[s] / float(n) for s in slots}
 
 
 class _StepPlan:
@@ -2100,3 +1874,6 @@ class _StepPlan:
         # callers keep per-step losses across later replays (engine_model.loss_acc): a ring row (valid for
         # LossRing.ROWS steps), else a copy
         return self.ring.last() if self.ring is not None else self.loss_sel.clone()
+
+
+HipResNetBackend._plan_cls = _StepPlan

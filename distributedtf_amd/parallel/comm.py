@@ -374,8 +374,8 @@ def shutdown_distributed():
     import sys
     import torch.distributed as dist
     _CTX.clear()
-    hr = sys.modules.get("distributedtf_amd.engine.hip_resnet")
-    if hr is not None and hr.release_graphs():
+    hs = sys.modules.get("distributedtf_amd.engine.hip_step")  # loaded iff a HIP backend was
+    if hs is not None and hs.release_graphs():
         import gc
         import torch
         gc.collect()

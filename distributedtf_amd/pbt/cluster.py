@@ -398,7 +398,7 @@ class SPMDPopulation(_ReportMixin):
                 self.worker.explore_time, float(dp.bytes_moved), dp.seconds, dp.transfers_done]
 
     def _graph_state(self):
-        from ..engine.hip_resnet import graph_state
+        from ..engine.hip_step import graph_state
         for g in self.worker.worker_graphs:
             eng = getattr(g, "engine", None)
             if eng is not None:

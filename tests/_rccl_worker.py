@@ -7,7 +7,7 @@ Modes (argv[1]):
            send/recv (parallel/dataplane.py, reference pbt_cluster.py:145-147) -> bit-exact rows, and the next
            captured step of a loser runs on the imported weights and step counter.
   dp       --dp_size 2: one member group of 2 ranks trains 2 members, the gradient all-reduce captured in the
-           HIP step graph (engine/hip_resnet.py run_captured); replicas must stay bitwise identical, and the
+           HIP step graph (engine/hip_step.py run_captured); replicas must stay bitwise identical, and the
            step must have run as a graph (no eager fallback).
 """
 
@@ -88,7 +88,7 @@ def run_exploit(comm, out):
         sa.update({int(k): v for k, v in sv.items()})
     out["all_losses_after"] = la
     out["all_steps_after"] = sa
-    from distributedtf_amd.engine.hip_resnet import graph_state
+    from distributedtf_amd.engine.hip_step import graph_state
     out["graph_state"] = graph_state(eng.backend)
 
 
@@ -96,7 +96,7 @@ def run_dp(comm, out):
     import torch
     from distributedtf_amd.pbt.cluster import SPMDPopulation
     from distributedtf_amd.models.cifar10_model import Cifar10Model
-    from distributedtf_amd.engine.hip_resnet import graph_state
+    from distributedtf_amd.engine.hip_step import graph_state
     hps = _hps(2, 5)
     pop = SPMDPopulation(2, comm, Cifar10Model, epochs_per_round=1, seed=5, verbose=False, hparams=hps, dp_size=2,
                          model_kwargs=dict(resnet_size=20, max_train_steps=4, use_synthetic_data=True,

@@ -42,12 +42,6 @@
 #ifndef DTF_FWD_COEFREG
 #define DTF_FWD_COEFREG 1  // conv_fwd_s1 MODE 1: BN scale / shift of the staged channels held in VGPRs (pop 8 3.078 -> 3.063 ms, profiles/r6_fwd_coefreg_ab.log)
 #endif
-#ifndef DTF_WGRAD_PF2
-#define DTF_WGRAD_PF2 0  // 1: deferred wgrad jobs with tiles prefetched two iterations ahead (conv_wgrad_pf2_body): measured +0.8 % at pop 8, flat at C = 16 only (profiles/r6_wgrad_pf2_ab.log)
-#endif
-#ifndef DTF_WGRAD_PF2_MAXC
-#define DTF_WGRAD_PF2_MAXC 64  // ... for the channel widths up to this
-#endif
 #ifndef DTF_COEF_SPLIT
 #define DTF_COEF_SPLIT 1  // C < 64: wave 0's 64 / C lane groups split the statistic replicas (shuffle-summed)
 #endif
@@ -760,64 +754,101 @@ __device__ __forceinline__ uint4 xform8r(uint4 v, uint4 v2, uint4 v3, int c0, co
   return make_uint4(w[0], w[1], w[2], w[3]);
 }
 
-// Compile-time tile geometry for a [RT][WP][C] (+8 pad per pixel) LDS tile of rows gy0..gy0+RT-1 and columns
-// -1..W of an H x W x C image.  Each thread owns MAXC 16-byte chunk slots (always the same 8 channels, since
-// 256 % (C/8) == 0); per slot: LDS offset, in-band global offset, and three bit masks (column/slot valid,
-// top halo row, bottom halo row) so an iteration only adds its band's row offset.  Inactive slots stage zeros
-// into pixel 0's pad lanes (never read), keeping load/store branch-free.
+// Compile-time tile geometry for a [RT][WP][C] (+ pad per pixel) LDS tile of rows gy0..gy0+RT-1 and columns
+// -1..W of an H x W x C image, staged in three parts:
+//  * band interior (tile rows 1..RT-2, image columns): (RT-2) * W * C/8 16-byte chunks = MAXC slots per thread, all
+//    of them always inside the image -- no mask, no dummy load; per slot the LDS offset and the in-band global offset
+//    are fixed for the launch, an iteration only adds its band's row offset.  A thread's slots always hold the same
+//    8 channels c0.. (256 % (C/8) == 0), which the register-held coefficients rely on;
+//  * halo rows (tile rows 0 and RT-1, image columns): 2 * W * C/8 = 128 chunks at every width, one per thread of
+//    wave 0 (top row) and wave 1 (bottom row), the same channels c0..; a row outside the image is written as zeros
+//    (wave-uniform).  Staged every iteration (a buffer alternates between band positions); when the image is a single
+//    band (H == RT-2) both rows are always zero and the pass is compiled out;
+//  * halo columns 0 and W+1 (and the halo rows of a single-band image): zero for the whole launch, written once by
+//    zero_border() in the prologue and never written again.
 template <int C, int RT, int W, int H, int CPV = cpad<C>(), int WPV = W + 2>
 struct Stage {
   static constexpr int WD = W + 2, WP = WPV, CP = CPV, NCH = C / 8, ROW = W * C;  // WD staged columns, WP pitch
   static_assert(WP >= WD, "row pitch covers the staged columns");
-  static constexpr int TOTAL = RT * WD * NCH, MAXC = (TOTAL + 255) / 256;
-  int loff[MAXC];
-  int goff[MAXC];
-  int roff[MAXC];  // band-interior chunks: offset in an unhaloed [RT-2][W][CP] tile (store_raw)
-  unsigned okm, top, bot;
+  static constexpr int MAXC = (RT - 2) / 4;  // 2 for the 8-row bands (512 interior chunks at every width)
+  static_assert((RT - 2) * W * NCH == MAXC * 256, "the band interior is exactly MAXC chunks per thread");
+  static_assert(2 * W * NCH == 128, "the two halo rows are one chunk per thread of waves 0 and 1");
+  static constexpr bool HALO = H > RT - 2;  // several bands per image: the halo rows can lie inside the image
+  // one operand's chunks of a tile in registers: the interior slots and (waves 0 / 1) the halo-row chunk
+  struct Regs {
+    uint4 v[MAXC];
+    uint4 h;
+  };
+  // slot 0's offsets: LDS tile (elements), global from tile row 0 = image row gy0 (bytes), unhaloed [RT-2][W][CP]
+  // tile of store_raw (elements).  Slot j is the same column and channels 4 band rows further (W * NCH == 64 chunks
+  // per row, 256 per slot): a compile-time distance
+  int loff0, goff0, roff0;
+  __device__ __forceinline__ int loff(int j) const { return loff0 + j * 4 * WP * CP; }
+  __device__ __forceinline__ int goff(int j) const { return goff0 + j * 4 * ROW * 2; }
+  __device__ __forceinline__ int roff(int j) const { return roff0 + j * 4 * W * CP; }
+  // wave index (uniform): 0 stages the top halo row, 1 the bottom one.  Thread t < 128 owns the halo-row chunk in
+  // the column and channels of its interior slot 0 (W * NCH == 64: slot 0 of wave w is band row w), so the chunk's
+  // offsets are slot 0's plus a wave-uniform row distance (hdl LDS elements, hdg bytes)
+  int hw, hdl, hdg;
   int c0;
   __device__ __forceinline__ void init() {
     c0 = (threadIdx.x % NCH) * 8;
-    okm = top = bot = 0;
-#pragma unroll
-    for (int j = 0; j < MAXC; ++j) {
-      const int idx = threadIdx.x + 256 * j;
-      const int pc = idx / NCH, col = pc % WD, r = pc / WD;
-      const bool act = idx < TOTAL;
-      loff[j] = act ? (r * WP + col) * CP + c0 : RT * WP * CP;  // inactive: the 8-element slack past the tile
-      roff[j] = ((r - 1) * W + (col - 1)) * CP + c0;
-      goff[j] = (r * ROW + (col - 1) * C + c0) * 2;  // bytes
-      if (act && col >= 1 && col <= W) okm |= 1u << j;
-      if (r == 0) top |= 1u << j;
-      if (r == RT - 1) bot |= 1u << j;
+    static_assert(W * NCH == 64, "one band row per wave and slot");
+    hw = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int col = (threadIdx.x & 63) / NCH;  // chunk threadIdx.x + 256 j: band row hw + 4 j, image column col
+    loff0 = ((hw + 1) * WP + col + 1) * CP + c0;
+    roff0 = (hw * W + col) * CP + c0;
+    goff0 = ((hw + 1) * ROW + col * C + c0) * 2;
+    const int hrows = hw == 0 ? -1 : RT - 3;  // tile row 0 from tile row 1, tile row RT-1 from tile row 2
+    hdl = hrows * WP * CP;
+    hdg = hrows * ROW * 2;
+  }
+  // this wave stages a halo row / that row lies inside the image (first tile row = gy0); both wave-uniform
+  __device__ __forceinline__ bool halo_wave() const { return hw < 2; }
+  __device__ __forceinline__ bool halo_in(int gy0) const { return hw == 0 ? gy0 >= 0 : gy0 + RT <= H; }
+  // The launch-constant zeros of one tile buffer (before the prologue's first barrier; staging never writes them).
+  static __device__ __forceinline__ void zero_border(bf16_t* buf) {
+    const uint4 z = make_uint4(0, 0, 0, 0);
+    for (int idx = threadIdx.x; idx < RT * 2 * NCH; idx += 256) {
+      const int ch = idx % NCH, pc = idx / NCH, r = pc >> 1, col = (pc & 1) ? W + 1 : 0;
+      *reinterpret_cast<uint4*>(buf + (r * WP + col) * CP + ch * 8) = z;
+    }
+    if constexpr (!HALO) {
+      if (threadIdx.x < 128) {
+        const int r = (threadIdx.x >> 6) ? RT - 1 : 0, col = (threadIdx.x & 63) / NCH, ch = threadIdx.x % NCH;
+        *reinterpret_cast<uint4*>(buf + (r * WP + col + 1) * CP + ch * 8) = z;
+      }
     }
   }
-  // first tile row = gy0; rows outside [0, H) are zero
-  __device__ __forceinline__ unsigned mask(int gy0) const {
-    unsigned m = okm;
-    if (gy0 < 0) m &= ~top;
-    if (gy0 + RT > H) m &= ~bot;
-    return m;
-  }
   template <int MODE>
-  __device__ __forceinline__ void load(uint4 (&v)[MAXC], uint4 (&v2)[MAXC], unsigned m, const bf16_t* img,
-                                       const bf16_t* img2, int gy0) const {
+  __device__ __forceinline__ void load(Regs& v, Regs& v2, const bf16_t* img, const bf16_t* img2, int gy0) const {
     // byte offsets in 32 bits: uniform base (SGPR) + lane offset -> saddr global loads
     const int rb = gy0 * ROW * 2;
 #pragma unroll
     for (int j = 0; j < MAXC; ++j) {
-      const uint32_t off = ((m >> j) & 1u) ? (uint32_t)(rb + goff[j]) : 0u;
-      v[j] = *reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(img) + off);
-      if constexpr (MODE >= 2) v2[j] = *reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(img2) + off);
+      const uint32_t off = (uint32_t)(rb + goff(j));
+      v.v[j] = *reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(img) + off);
+      if constexpr (MODE >= 2) v2.v[j] = *reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(img2) + off);
+    }
+    if constexpr (HALO) {
+      if (halo_wave() && halo_in(gy0)) {
+        const uint32_t off = (uint32_t)(rb + hdg + goff(0));
+        v.h = *reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(img) + off);
+        if constexpr (MODE >= 2) v2.h = *reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(img2) + off);
+      }
     }
   }
   template <int MODE>
-  __device__ __forceinline__ void store(bf16_t* buf, const uint4 (&v)[MAXC], const uint4 (&v2)[MAXC], unsigned m,
-                                        const float* coef) const {
+  __device__ __forceinline__ void store(bf16_t* buf, const Regs& v, const Regs& v2, int gy0, const float* coef) const {
 #pragma unroll
-    for (int j = 0; j < MAXC; ++j) {
-      uint4 t = make_uint4(0, 0, 0, 0);
-      if ((m >> j) & 1u) t = xform8<MODE>(v[j], v2[j], c0, coef);
-      *reinterpret_cast<uint4*>(buf + loff[j]) = t;
+    for (int j = 0; j < MAXC; ++j)
+      *reinterpret_cast<uint4*>(buf + loff(j)) = xform8<MODE>(v.v[j], v2.v[j], c0, coef);
+    if constexpr (HALO) {
+      if (halo_wave()) {
+        uint4 t = make_uint4(0, 0, 0, 0);
+        if (halo_in(gy0)) t = xform8<MODE>(v.h, v2.h, c0, coef);
+        *reinterpret_cast<uint4*>(buf + hdl + loff(0)) = t;
+      }
     }
   }
   // MODE 1 with the thread's 8 scale / shift coefficients in registers (its channels c0..c0+7 are the same for
@@ -829,20 +860,23 @@ struct Stage {
       sh[i] = coef[64 + c0 + i];
     }
   }
-  __device__ __forceinline__ void store1r(bf16_t* buf, const uint4 (&v)[MAXC], unsigned m, const float (&sc)[8],
+  static __device__ __forceinline__ uint4 xform1r(uint4 v, const float (&sc)[8], const float (&sh)[8]) {
+    uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+      w[q] = relu_pk2(pk2(unpk2(w[q]) * (f32x2_t){sc[2 * q], sc[2 * q + 1]} + (f32x2_t){sh[2 * q], sh[2 * q + 1]}));
+    return make_uint4(w[0], w[1], w[2], w[3]);
+  }
+  __device__ __forceinline__ void store1r(bf16_t* buf, const Regs& v, int gy0, const float (&sc)[8],
                                          const float (&sh)[8]) const {
 #pragma unroll
-    for (int j = 0; j < MAXC; ++j) {
-      uint4 t = make_uint4(0, 0, 0, 0);
-      if ((m >> j) & 1u) {
-        uint32_t w[4] = {v[j].x, v[j].y, v[j].z, v[j].w};
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-          w[q] = relu_pk2(pk2(unpk2(w[q]) * (f32x2_t){sc[2 * q], sc[2 * q + 1]} +
-                              (f32x2_t){sh[2 * q], sh[2 * q + 1]}));
-        t = make_uint4(w[0], w[1], w[2], w[3]);
+    for (int j = 0; j < MAXC; ++j) *reinterpret_cast<uint4*>(buf + loff(j)) = xform1r(v.v[j], sc, sh);
+    if constexpr (HALO) {
+      if (halo_wave()) {
+        uint4 t = make_uint4(0, 0, 0, 0);
+        if (halo_in(gy0)) t = xform1r(v.h, sc, sh);
+        *reinterpret_cast<uint4*>(buf + hdl + loff(0)) = t;
       }
-      *reinterpret_cast<uint4*>(buf + loff[j]) = t;
     }
   }
   // MODE 2 / 3 coefficients of the thread's 8 channels (A, B, C of xform8r) in registers
@@ -854,53 +888,57 @@ struct Stage {
       kc[i] = coef[128 + c0 + i];
     }
   }
-  // The untransformed band-interior chunks (tile rows 1..RT-2, image columns) into `raw` ([RT-2][W][CP]).
-  __device__ __forceinline__ void store_raw(bf16_t* raw, const uint4 (&v)[MAXC], unsigned m) const {
-    const unsigned interior = m & ~top & ~bot;
+  // The untransformed band interior into `raw` ([RT-2][W][CP]).
+  __device__ __forceinline__ void store_raw(bf16_t* raw, const Regs& v) const {
 #pragma unroll
-    for (int j = 0; j < MAXC; ++j)
-      if ((interior >> j) & 1u) *reinterpret_cast<uint4*>(raw + roff[j]) = v[j];
+    for (int j = 0; j < MAXC; ++j) *reinterpret_cast<uint4*>(raw + roff(j)) = v.v[j];
   }
-  // MODE 2 / 3 (BN-backward apply [+ residual v3]) staging that also writes the transformed band-interior
-  // chunks (tile rows 1..RT-2, image columns) to `out` (the image base; null: LDS only).
-  // (KR: the coefficients come from ka / kb / kc -- load_coef3 -- instead of LDS)
+  // BN-backward apply [+ residual v3] of one chunk (KR: coefficients from ka / kb / kc -- load_coef3 -- not LDS)
+  template <int MODE, bool KR>
+  __device__ __forceinline__ uint4 xform_x(uint4 v, uint4 v2, uint4 v3, const float* coef, const float* ka,
+                                           const float* kb, const float* kc) const {
+    if constexpr (KR) {
+      const uint32_t w[4] = {v.x, v.y, v.z, v.w}, h[4] = {v2.x, v2.y, v2.z, v2.w}, r[4] = {v3.x, v3.y, v3.z, v3.w};
+      uint32_t o[4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        f32x2_t u = unpk2(w[q]) * (f32x2_t){ka[2 * q], ka[2 * q + 1]} +
+                    unpk2(h[q]) * (f32x2_t){kb[2 * q], kb[2 * q + 1]} + (f32x2_t){kc[2 * q], kc[2 * q + 1]};
+        if constexpr (MODE == 3) u += unpk2(r[q]);
+        o[q] = pk2(u);
+      }
+      return make_uint4(o[0], o[1], o[2], o[3]);
+    } else {
+      return xform8r<MODE>(v, v2, v3, c0, coef);
+    }
+  }
+  // MODE 2 / 3 (BN-backward apply [+ residual v3]) staging that also writes the transformed band interior to
+  // `out` (the image base; null: LDS only); the halo rows go to LDS only.
   template <int MODE, bool KR = false>
-  __device__ __forceinline__ void store_x(bf16_t* buf, const uint4 (&v)[MAXC], const uint4 (&v2)[MAXC],
-                                          const uint4 (&v3)[MAXC], unsigned m, const float* coef, bf16_t* out,
-                                          int gy0, const float* ka = nullptr, const float* kb = nullptr,
-                                          const float* kc = nullptr) const {
-    const unsigned interior = m & ~top & ~bot;
+  __device__ __forceinline__ void store_x(bf16_t* buf, const Regs& v, const Regs& v2, const Regs& v3, int gy0,
+                                          const float* coef, bf16_t* out, const float* ka = nullptr,
+                                          const float* kb = nullptr, const float* kc = nullptr) const {
     const int rb = gy0 * ROW * 2;
 #if DTF_WT_ACT
     const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(out, 0, H * ROW * 2, 0x00020000);  // one image
 #endif
 #pragma unroll
     for (int j = 0; j < MAXC; ++j) {
-      uint4 t = make_uint4(0, 0, 0, 0);
-      if ((m >> j) & 1u) {
-        if constexpr (KR) {
-          const uint32_t w[4] = {v[j].x, v[j].y, v[j].z, v[j].w}, h[4] = {v2[j].x, v2[j].y, v2[j].z, v2[j].w},
-                         r[4] = {v3[j].x, v3[j].y, v3[j].z, v3[j].w};
-          uint32_t o[4];
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            f32x2_t u = unpk2(w[q]) * (f32x2_t){ka[2 * q], ka[2 * q + 1]} +
-                        unpk2(h[q]) * (f32x2_t){kb[2 * q], kb[2 * q + 1]} + (f32x2_t){kc[2 * q], kc[2 * q + 1]};
-            if constexpr (MODE == 3) u += unpk2(r[q]);
-            o[q] = pk2(u);
-          }
-          t = make_uint4(o[0], o[1], o[2], o[3]);
-        } else {
-          t = xform8r<MODE>(v[j], v2[j], v3[j], c0, coef);
-        }
-      }
-      *reinterpret_cast<uint4*>(buf + loff[j]) = t;
-      if (out != nullptr && ((interior >> j) & 1u)) {
+      const uint4 t = xform_x<MODE, KR>(v.v[j], v2.v[j], v3.v[j], coef, ka, kb, kc);
+      *reinterpret_cast<uint4*>(buf + loff(j)) = t;
+      if (out != nullptr) {
 #if DTF_WT_ACT
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, t), rsrc, rb + goff[j], 0, 16);  // sc1
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, t), rsrc, rb + goff(j), 0, 16);  // sc1
 #else
-        *reinterpret_cast<uint4*>(reinterpret_cast<char*>(out) + (uint32_t)(rb + goff[j])) = t;
+        *reinterpret_cast<uint4*>(reinterpret_cast<char*>(out) + (uint32_t)(rb + goff(j))) = t;
 #endif
+      }
+    }
+    if constexpr (HALO) {
+      if (halo_wave()) {
+        uint4 t = make_uint4(0, 0, 0, 0);
+        if (halo_in(gy0)) t = xform_x<MODE, KR>(v.h, v2.h, v3.h, coef, ka, kb, kc);
+        *reinterpret_cast<uint4*>(buf + hdl + loff(0)) = t;
       }
     }
   }
@@ -1054,13 +1092,12 @@ __device__ __forceinline__ void conv_fwd_s1_body(const ConvArgs& a, const int bi
   constexpr int NT = C / 16, WPT = 4 / NT;  // NT: output-channel tiles
   constexpr int KTOT = 9 * C, KS = (KTOT + 31) / 32;
   constexpr int CP = cpad_fwd<C>(), RT = ROWS + 2, WP = wpitch<C>();
-  constexpr int TSZ = (RT * WP * CP + 8 + 63) & ~63;  // + slack for inactive staging slots
+  constexpr int TSZ = (RT * WP * CP + 8 + 63) & ~63;  // (the host sizes the launch's LDS with the same formula)
   constexpr int NTILES = ROWS * W / 16;
   constexpr int MT = NTILES / WPT;  // output pixel tiles per wave per iteration
   static_assert(NTILES == WPT * MT && MT <= MAXT, "every wave owns MT output tiles");
   constexpr int ROW = W * C, IMG = H * ROW;
   using St = Stage<C, RT, W, H, CP, WP>;
-  constexpr int MAXC = St::MAXC;
   constexpr int LMODE = MODE_IN == 0 ? 0 : 1;
   float* coef = reinterpret_cast<float*>(smem);  // 192 floats
   float* acc_lds = coef + 192;                   // 128 floats
@@ -1095,13 +1132,9 @@ __device__ __forceinline__ void conv_fwd_s1_body(const ConvArgs& a, const int bi
   const float n_in = cnt[slot] * (float)(H * W);
   St st;
   st.init();
-  uint4 tv[MAXC], unused[MAXC];
-  unsigned tm;
-  {
-    const int img = it0 / BANDS, gy0 = (it0 % BANDS) * ROWS - 1;
-    tm = st.mask(gy0);
-    st.template load<LMODE>(tv, unused, tm, xin + img * IMG, nullptr, gy0);
-  }
+  typename St::Regs tv, unused;
+  int tgy0 = (it0 % BANDS) * ROWS - 1;  // first tile row of the tile in tv
+  st.template load<LMODE>(tv, unused, xin + (it0 / BANDS) * IMG, nullptr, tgy0);
   bf16x8_t afr[KS];
   {
     const bf16_t* wb = wgt + (long)slot * w_mstride + w_off + (long)(ct * 16 + (lane & 15)) * KTOT;
@@ -1116,6 +1149,8 @@ __device__ __forceinline__ void conv_fwd_s1_body(const ConvArgs& a, const int bi
   coef_reduce<C, MODE_IN == 0 ? 0 : 1>(cl);
   coef_finish<C, MODE_IN == 0 ? 0 : 1>(coef, cl, n_in);
   if (threadIdx.x < 128) acc_lds[threadIdx.x] = 0.f;
+  St::zero_border(SBUF(0));
+  St::zero_border(SBUF(1));
   int tapoff[KS];  // k-chunks past KTOT have zero weights and read a valid in-tile address
 #pragma unroll
   for (int s = 0; s < KS; ++s) {
@@ -1148,9 +1183,9 @@ __device__ __forceinline__ void conv_fwd_s1_body(const ConvArgs& a, const int bi
   float csc[8], csh[8];
   if constexpr (CREG) {
     st.load_coef1(csc, csh, coef);
-    st.store1r(SBUF(0), tv, tm, csc, csh);
+    st.store1r(SBUF(0), tv, tgy0, csc, csh);
   } else {
-    st.template store<LMODE>(SBUF(0), tv, unused, tm, coef);
+    st.template store<LMODE>(SBUF(0), tv, unused, tgy0, coef);
   }
   __syncthreads();
   STAMP(2);
@@ -1165,9 +1200,9 @@ __device__ __forceinline__ void conv_fwd_s1_body(const ConvArgs& a, const int bi
       for (int i = 0; i < MT; ++i) rres[i] = nres[i];
     }
     if (more) {
-      const int nimg = (it + 1) / BANDS, ngy0 = ((it + 1) % BANDS) * ROWS - 1;
-      tm = st.mask(ngy0);
-      st.template load<LMODE>(tv, unused, tm, a.x + nimg * IMG, nullptr, ngy0);
+      const int nimg = (it + 1) / BANDS;
+      tgy0 = ((it + 1) % BANDS) * ROWS - 1;
+      st.template load<LMODE>(tv, unused, a.x + nimg * IMG, nullptr, tgy0);
       if constexpr (RESID) {
         const long nband = (long)nimg * IMG + ((it + 1) % BANDS) * ROWS * ROW;
 #pragma unroll
@@ -1198,9 +1233,9 @@ __device__ __forceinline__ void conv_fwd_s1_body(const ConvArgs& a, const int bi
     }
     if (more) {
       if constexpr (CREG)
-        st.store1r(SBUF(k + 1), tv, tm, csc, csh);
+        st.store1r(SBUF(k + 1), tv, tgy0, csc, csh);
       else
-        st.template store<LMODE>(SBUF(k + 1), tv, unused, tm, coef);
+        st.template store<LMODE>(SBUF(k + 1), tv, unused, tgy0, coef);
     }
     __syncthreads();
   }
@@ -1803,14 +1838,13 @@ __device__ __forceinline__ void conv_bwd_body(const ConvArgs& a, const int bid, 
   constexpr int NTN = 9 * C / 16;      // wgrad (tap, ci) tiles
   constexpr int NJ = (NTN + 3) / 4;
   constexpr int CP = cpad<C>(), RT = ROWS + 2, WP = wpitch<C>();
-  constexpr int TSZ = (RT * WP * CP + 8 + 63) & ~63;  // + slack for inactive staging slots
+  constexpr int TSZ = (RT * WP * CP + 8 + 63) & ~63;  // (the host sizes the launch's LDS with the same formula)
   constexpr int NTILES = ROWS * W / 16;
   constexpr int MTD = NTILES / WPT;  // dgrad tiles per wave (MAXT for 8-row bands)
   static_assert(NTILES == WPT * MTD && MTD <= MAXT, "every wave owns MTD dgrad tiles");
   constexpr int ROW = W * C, IMG = H * ROW;
   constexpr int NK = ROWS * W / 32, RSTEP = 32 / W, KINC = RSTEP * WP * CP;
   using St = Stage<C, RT, W, H, CP, WP>;
-  constexpr int MAXC = St::MAXC;
   float* coef_d = reinterpret_cast<float*>(smem);  // dy transform (192)
   float* ecoef = coef_d + 192;                     // x BN: scale, shift, -mean*inv, inv (256)
   float* acc_lds = ecoef + 256;                    // 128
@@ -1889,15 +1923,11 @@ __device__ __forceinline__ void conv_bwd_body(const ConvArgs& a, const int bid, 
   st.init();
   // MODE_DY 3: dY = BN-backward(x, x2) + x3; with xout the transformed band interior is also written out
   constexpr bool XSTORE = MODE_DY >= 2;
-  uint4 dv[MAXC], dv2[MAXC], dv3[MAXC], xv_[MAXC], unused[MAXC];  // dv3: MODE_DY 3 only
-  unsigned dm, xm;
+  typename St::Regs dv, dv2, dv3, xv_, unused;  // dv3: MODE_DY 3 only
   int cimg = it0 / BANDS, cgy0 = (it0 % BANDS) * ROWS - 1;  // image / first tile row of the staged tile
-  {
-    dm = xm = st.mask(cgy0);
-    st.template load<MODE_DY == 3 ? 2 : MODE_DY>(dv, dv2, dm, k_x + cimg * IMG, k_x2 + cimg * IMG, cgy0);
-    if constexpr (MODE_DY == 3) st.template load<0>(dv3, unused, dm, k_x3 + cimg * IMG, nullptr, cgy0);
-    if constexpr (WG) st.template load<1>(xv_, unused, xm, k_xm + cimg * IMG, nullptr, cgy0);
-  }
+  st.template load<MODE_DY == 3 ? 2 : MODE_DY>(dv, dv2, k_x + cimg * IMG, k_x2 + cimg * IMG, cgy0);
+  if constexpr (MODE_DY == 3) st.template load<0>(dv3, unused, k_x3 + cimg * IMG, nullptr, cgy0);
+  if constexpr (WG) st.template load<1>(xv_, unused, k_xm + cimg * IMG, nullptr, cgy0);
   STAMP_FINE(10);
   // WLDS (C = 16: all four waves share the 16 x 144 weights): the weights are staged once into LDS rows of
   // WLP elements (zero past KTOT) and read per MFMA, freeing the 20 VGPRs of afr for the pipelines
@@ -1948,6 +1978,13 @@ __device__ __forceinline__ void conv_bwd_body(const ConvArgs& a, const int bid, 
       ecoef[192 + c] = inv;
     }
     if (threadIdx.x < 128) acc_lds[threadIdx.x] = 0.f;
+  }
+  // the launch-constant zero border of every tile buffer in use
+  St::zero_border(FDBUF(0));
+  if constexpr (WG) St::zero_border(FXBUF(0));
+  if constexpr (!SB) {
+    St::zero_border(FDBUF(1));
+    if constexpr (WG) St::zero_border(FXBUF(1));
   }
   if constexpr (WLDS) {
 #pragma unroll
@@ -2023,16 +2060,15 @@ __device__ __forceinline__ void conv_bwd_body(const ConvArgs& a, const int bid, 
   if constexpr (KREG_D) st.load_coef3(ka, kb, kc, coef_d);
   if constexpr (KREG_X) st.load_coef1(xsc, xsh, ecoef);
   if constexpr (XSTORE)  // (the wgrad role stages the same transform but never writes xout)
-    st.template store_x<MODE_DY == 3 ? 3 : 2, KREG_D>(FDBUF(0), dv, dv2, dv3, dm, coef_d,
-                                                      (DG && k_xout) ? k_xout + cimg * IMG : nullptr, cgy0, ka, kb,
-                                                      kc);
+    st.template store_x<MODE_DY == 3 ? 3 : 2, KREG_D>(FDBUF(0), dv, dv2, dv3, cgy0, coef_d,
+                                                      (DG && k_xout) ? k_xout + cimg * IMG : nullptr, ka, kb, kc);
   else
-    st.template store<MODE_DY>(FDBUF(0), dv, dv2, dm, coef_d);
+    st.template store<MODE_DY>(FDBUF(0), dv, dv2, cgy0, coef_d);
   if constexpr (KREG_X)
-    st.store1r(FXBUF(0), xv_, xm, xsc, xsh);
+    st.store1r(FXBUF(0), xv_, cgy0, xsc, xsh);
   else if constexpr (WG)
-    st.template store<1>(FXBUF(0), xv_, unused, xm, ecoef);
-  if constexpr (RAWX) st.store_raw(FXRAW(0), xv_, xm);
+    st.template store<1>(FXBUF(0), xv_, unused, cgy0, ecoef);
+  if constexpr (RAWX) st.store_raw(FXRAW(0), xv_);
   f32x2_t esc0, esc1, esh0, esh1, enm0, enm1, eiv0, eiv1;
   if constexpr (KREG_E) {
     esc0 = lds2(ecoef + ci0), esc1 = lds2(ecoef + ci0 + 2);
@@ -2063,10 +2099,9 @@ __device__ __forceinline__ void conv_bwd_body(const ConvArgs& a, const int bid, 
     if (more) {
       cimg = (it + 1) / BANDS;
       cgy0 = ((it + 1) % BANDS) * ROWS - 1;
-      dm = xm = st.mask(cgy0);
-      st.template load<MODE_DY == 3 ? 2 : MODE_DY>(dv, dv2, dm, k_x + cimg * IMG, k_x2 + cimg * IMG, cgy0);
-      if constexpr (MODE_DY == 3) st.template load<0>(dv3, unused, dm, k_x3 + cimg * IMG, nullptr, cgy0);
-      if constexpr (WG) st.template load<1>(xv_, unused, xm, k_xm + cimg * IMG, nullptr, cgy0);
+      st.template load<MODE_DY == 3 ? 2 : MODE_DY>(dv, dv2, k_x + cimg * IMG, k_x2 + cimg * IMG, cgy0);
+      if constexpr (MODE_DY == 3) st.template load<0>(dv3, unused, k_x3 + cimg * IMG, nullptr, cgy0);
+      if constexpr (WG) st.template load<1>(xv_, unused, k_xm + cimg * IMG, nullptr, cgy0);
       if constexpr (DG) epi_load(it + 1);
     }
     const bf16_t* dcur = FDBUF(k);
@@ -2143,16 +2178,15 @@ __device__ __forceinline__ void conv_bwd_body(const ConvArgs& a, const int bid, 
     if (more) {
       if constexpr (SB) __syncthreads();  // every wave is done with the current tiles
       if constexpr (XSTORE)
-        st.template store_x<MODE_DY == 3 ? 3 : 2, KREG_D>(FDBUF(k + 1), dv, dv2, dv3, dm, coef_d,
-                                                          (DG && k_xout) ? k_xout + cimg * IMG : nullptr, cgy0, ka,
-                                                          kb, kc);
+        st.template store_x<MODE_DY == 3 ? 3 : 2, KREG_D>(FDBUF(k + 1), dv, dv2, dv3, cgy0, coef_d,
+                                                          (DG && k_xout) ? k_xout + cimg * IMG : nullptr, ka, kb, kc);
       else
-        st.template store<MODE_DY>(FDBUF(k + 1), dv, dv2, dm, coef_d);
+        st.template store<MODE_DY>(FDBUF(k + 1), dv, dv2, cgy0, coef_d);
       if constexpr (KREG_X)
-        st.store1r(FXBUF(k + 1), xv_, xm, xsc, xsh);
+        st.store1r(FXBUF(k + 1), xv_, cgy0, xsc, xsh);
       else if constexpr (WG)
-        st.template store<1>(FXBUF(k + 1), xv_, unused, xm, ecoef);
-      if constexpr (RAWX) st.store_raw(FXRAW(k + 1), xv_, xm);
+        st.template store<1>(FXBUF(k + 1), xv_, unused, cgy0, ecoef);
+      if constexpr (RAWX) st.store_raw(FXRAW(k + 1), xv_);
     }
     __syncthreads();
   }
@@ -2210,183 +2244,6 @@ __device__ __forceinline__ void conv_bwd_body(const ConvArgs& a, const int bid, 
   }
   STAMP_DRAIN(5);
   STAMP_FLUSH(a.cin_real, nit);
-}
-
-// Weight-gradient role with the input tiles prefetched TWO (image, band) iterations ahead (two register sets; the
-// loop unrolled by two so each set is a compile-time array).  Same operands, staging transforms, MFMA order and slab
-// layout as conv_bwd_body<C, MODE_DY, 0, 2> -- bitwise the same partials -- for the deferred jobs of
-// conv_wgrad_all_kernel: one round of staging loads in flight behind the MFMAs was not enough to cover the L2 /
-// MALL latency of these 1-2-workgroups-per-CU launches (C = 64: ~1 TB/s of traffic, 3x its MFMA + HBM floor).
-template <int C, int MODE_DY>
-__device__ __forceinline__ void conv_wgrad_pf2_body(const ConvArgs& a, const int bid, char* smem) {
-  static_assert(MODE_DY == 0 || MODE_DY == 2, "deferred wgrad jobs: plain dY or BN-backward(dz, h)");
-  constexpr int ROWS = 8, W = 512 / C, H = W, BANDS = H / ROWS;
-  constexpr int MT = C / 16, NTN = 9 * C / 16, NJ = (NTN + 3) / 4;
-  constexpr int CP = cpad<C>(), RT = ROWS + 2, WP = wpitch<C>();
-  constexpr int TSZ = (RT * WP * CP + 8 + 63) & ~63;
-  constexpr int IMG = H * W * C;
-  constexpr int NK = ROWS * W / 32, RSTEP = 32 / W, KINC = RSTEP * WP * CP;
-  using St = Stage<C, RT, W, H, CP, WP>;
-  constexpr int MAXC = St::MAXC;
-  float* coef_d = reinterpret_cast<float*>(smem);
-  float* ecoef = coef_d + 192;
-  bf16_t* t0 = reinterpret_cast<bf16_t*>(smem + 2304);
-#define PDBUF(i) (t0 + ((i) & 1) * 2 * TSZ)
-#define PXBUF(i) (t0 + TSZ + ((i) & 1) * 2 * TSZ)
-  const bf16_t* k_x = a.x;
-  const bf16_t* k_x2 = a.x2;
-  const bf16_t* k_xm = a.xm;
-  const float* k_st_in = a.st_in;
-  const float* k_st_in_b = a.st_in_b;
-  const float* k_st_ep = a.st_ep;
-  const float* k_params = a.params;
-  const float* k_cnt = a.cnt;
-  float* k_slab = a.slab;
-  float* k_grads = a.grads;
-  const int4* k_work = a.work;
-  int k_in_gamma = a.in_gamma, k_in_beta = a.in_beta, k_ep_gamma = a.ep_gamma, k_ep_beta = a.ep_beta;
-  long k_p_mstride = a.p_mstride, k_g_mstride = a.g_mstride, k_g_off = a.g_off;
-  int k_u_items = a.u_items, k_u_chunk = a.u_chunk, k_u_per = a.u_per;
-  kpin(k_x); kpin(k_x2); kpin(k_xm); kpin(k_st_in); kpin(k_st_in_b); kpin(k_st_ep); kpin(k_params); kpin(k_cnt);
-  kpin(k_slab); kpin(k_grads); kpin(k_work); kpin(k_in_gamma); kpin(k_in_beta); kpin(k_ep_gamma); kpin(k_ep_beta);
-  kpin(k_p_mstride); kpin(k_g_mstride); kpin(k_g_off); kpin(k_u_items); kpin(k_u_chunk); kpin(k_u_per);
-  int4 wk;
-  if (k_u_items > 0) {
-    const int m = bid / k_u_items, kk = bid - m * k_u_items, it0_ = kk * k_u_chunk;
-    wk = make_int4(m * k_u_per + it0_, min(k_u_chunk, k_u_per - it0_), 0, m);
-  } else {
-    wk = k_work[bid];
-    wk = make_int4(__builtin_amdgcn_readfirstlane(wk.x), __builtin_amdgcn_readfirstlane(wk.y),
-                   __builtin_amdgcn_readfirstlane(wk.z), __builtin_amdgcn_readfirstlane(wk.w));
-  }
-  DTF_WG_CHECK(wk.x >= 0 && wk.y >= 0 && wk.w >= 0 && wk.z >= 0 && a.Hi > 0 && a.Wi > 0 && a.rows > 0);
-  const int it0 = wk.x, nit = wk.y, slot = wk.w;
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  CoefLd<MODE_DY == 0 ? 0 : 2> cld;
-  coef_issue<C, MODE_DY == 0 ? 0 : 2>(cld, k_params, k_p_mstride, slot, k_st_in, k_st_in_b, k_in_gamma, k_in_beta);
-  CoefLd<1> cle;
-  coef_issue<C, 1>(cle, k_params, k_p_mstride, slot, k_st_ep, nullptr, k_ep_gamma, k_ep_beta);
-  const float n_hw = k_cnt[slot] * (float)(H * W);
-  St st;
-  st.init();
-  // two register sets: set A holds the even iterations' tiles, set B the odd ones
-  uint4 dA[MAXC], d2A[MAXC], xA[MAXC], dB[MAXC], d2B[MAXC], xB[MAXC], unused[MAXC];
-  unsigned mA = 0, mB = 0;
-  int gA = 0, gB = 0;  // first tile row of the staged band (for the staging masks)
-  auto issue = [&](int it, uint4 (&d)[MAXC], uint4 (&d2)[MAXC], uint4 (&xv)[MAXC], unsigned& m, int& gy0) {
-    const int img = it / BANDS;
-    gy0 = (it % BANDS) * ROWS - 1;
-    m = st.mask(gy0);
-    st.template load<MODE_DY>(d, d2, m, k_x + img * IMG, k_x2 + img * IMG, gy0);
-    st.template load<1>(xv, unused, m, k_xm + img * IMG, nullptr, gy0);
-  };
-  auto put = [&](int k, const uint4 (&d)[MAXC], const uint4 (&d2)[MAXC], const uint4 (&xv)[MAXC], unsigned m,
-                 int gy0) {
-    if constexpr (MODE_DY >= 2)
-      st.template store_x<2>(PDBUF(k), d, d2, unused, m, coef_d, nullptr, gy0);
-    else
-      st.template store<MODE_DY>(PDBUF(k), d, d2, m, coef_d);
-    st.template store<1>(PXBUF(k), xv, unused, m, ecoef);
-  };
-  issue(it0, dA, d2A, xA, mA, gA);
-  if (nit > 1) issue(it0 + 1, dB, d2B, xB, mB, gB);
-  coef_reduce<C, MODE_DY == 0 ? 0 : 2>(cld);
-  coef_reduce<C, 1>(cle);
-  coef_finish<C, MODE_DY == 0 ? 0 : 2>(coef_d, cld, n_hw);
-  if (threadIdx.x < C) {
-    float mean, inv;
-    coef_moments<1>(cle, n_hw, mean, inv);
-    const float scale = cle.g * inv;
-    ecoef[threadIdx.x] = scale;
-    ecoef[64 + threadIdx.x] = cle.b - mean * scale;
-  }
-  const int g = lane >> 4, q = (lane & 15) >> 2, p4 = lane & 3;
-  const int pa = 8 * g + q, pb = pa + 4;
-  const int da_off = ((pa / W + 1) * WP + pa % W + 1) * CP + 4 * p4;
-  const int db_off = ((pb / W + 1) * WP + pb % W + 1) * CP + 4 * p4;
-  const int xa_off = ((pa / W) * WP + pa % W) * CP + 4 * p4, xb_off = ((pb / W) * WP + pb % W) * CP + 4 * p4;
-  int boff[NJ];
-#pragma unroll
-  for (int j = 0; j < NJ; ++j) {
-    const int nt = min(wave + 4 * j, NTN - 1);
-    const int tap = (nt * 16) / C, cb = (nt * 16) % C;
-    boff[j] = ((tap / 3) * WP + (tap % 3)) * CP + cb;
-  }
-  f32x4_t wacc[NJ][MT];
-#pragma unroll
-  for (int j = 0; j < NJ; ++j)
-#pragma unroll
-    for (int m = 0; m < MT; ++m) wacc[j][m] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
-  __syncthreads();  // coefficients
-  put(0, dA, d2A, xA, mA, gA);
-  __syncthreads();
-  auto mfmas = [&](int k) {
-    const bf16_t* dcur = PDBUF(k);
-    const bf16_t* xcur = PXBUF(k);
-#pragma unroll
-    for (int ks = 0; ks < NK; ++ks) {
-      bf16x8_t af[MT];
-#pragma unroll
-      for (int m = 0; m < MT; ++m) {
-        s16x4_t lo = ds_read_tr(dcur + da_off + ks * KINC + m * 16);
-        s16x4_t hi = ds_read_tr(dcur + db_off + ks * KINC + m * 16);
-        af[m] = (bf16x8_t){lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-      }
-      bf16x8_t bfr[NJ];
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) {
-        s16x4_t lo = ds_read_tr(xcur + xa_off + ks * KINC + boff[j]);
-        s16x4_t hi = ds_read_tr(xcur + xb_off + ks * KINC + boff[j]);
-        bfr[j] = (bf16x8_t){lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-      }
-#pragma unroll
-      for (int j = 0; j < NJ; ++j)
-#pragma unroll
-        for (int m = 0; m < MT; ++m) wacc[j][m] = mfma16(af[m], bfr[j], wacc[j][m]);
-    }
-  };
-  // iteration k: tiles of k + 1 sit in the other register set (loaded an iteration ago), k + 2 is issued into the set
-  // that held k (already in LDS)
-  for (int k = 0; k < nit; k += 2) {
-    if (k + 2 < nit) issue(it0 + k + 2, dA, d2A, xA, mA, gA);
-    mfmas(k);
-    if (k + 1 < nit) put(k + 1, dB, d2B, xB, mB, gB);
-    __syncthreads();
-    if (k + 1 >= nit) break;
-    if (k + 3 < nit) issue(it0 + k + 3, dB, d2B, xB, mB, gB);
-    mfmas(k + 1);
-    if (k + 2 < nit) put(k + 2, dA, d2A, xA, mA, gA);
-    __syncthreads();
-  }
-#undef PDBUF
-#undef PXBUF
-  if (k_slab) {
-    const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(k_slab + (long)bid * (NJ * MT * 4 * 256), 0,
-                                                       NJ * MT * 4 * 256 * 4, 0x00020000);
-#pragma unroll
-    for (int j = 0; j < NJ; ++j)
-#pragma unroll
-      for (int m = 0; m < MT; ++m)
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, wacc[j][m]), rsrc,
-                                               (((j * MT + m) * 256) + (int)threadIdx.x) * 16, 0, 16);
-    return;
-  }
-  float* gb = k_grads + (long)slot * k_g_mstride + k_g_off;
-#pragma unroll
-  for (int j = 0; j < NJ; ++j) {
-    const int nt = wave + 4 * j;
-    if (nt < NTN) {
-      const int tap = (nt * 16) / C, ci = (nt * 16) % C + (lane & 15);
-#pragma unroll
-      for (int m = 0; m < MT; ++m) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int co = m * 16 + 4 * (lane >> 4) + r;
-          atomicAdd(gb + ((long)co * 9 + tap) * C + ci, wacc[j][m][r]);
-        }
-      }
-    }
-  }
 }
 
 // Trailing workgroups of a backward launch: dW slab reduction of the PREVIOUS launch (r = index among them).
@@ -2453,20 +2310,10 @@ __global__ __launch_bounds__(256, 1) void conv_wgrad_all_kernel(const ConvArgs* 
   const int4 m = map[blockIdx.x];
   const int j = __builtin_amdgcn_readfirstlane(m.x), bid = __builtin_amdgcn_readfirstlane(m.y);
   const int c = __builtin_amdgcn_readfirstlane(m.z), mode = __builtin_amdgcn_readfirstlane(m.w);
-  // (the <64, 32> kernel runs one wave per SIMD either way: 300 VGPRs one-ahead, 502 with the two C = 64 register
-  // sets; <16, 16> stays LDS-bound at 3 workgroups per CU: 108 -> 140 VGPRs)
   if (c == CA) {
-    if constexpr (DTF_WGRAD_PF2 && CA <= DTF_WGRAD_PF2_MAXC) {
-      if (mode == 0) conv_wgrad_pf2_body<CA, 0>(jobs[j], bid, smem); else conv_wgrad_pf2_body<CA, 2>(jobs[j], bid, smem);
-    } else {
-      if (mode == 0) conv_bwd_body<CA, 0, 0, 2>(jobs[j], bid, smem); else conv_bwd_body<CA, 2, 0, 2>(jobs[j], bid, smem);
-    }
+    if (mode == 0) conv_bwd_body<CA, 0, 0, 2>(jobs[j], bid, smem); else conv_bwd_body<CA, 2, 0, 2>(jobs[j], bid, smem);
   } else if constexpr (CB != CA) {
-    if constexpr (DTF_WGRAD_PF2 && CB <= DTF_WGRAD_PF2_MAXC) {
-      if (mode == 0) conv_wgrad_pf2_body<CB, 0>(jobs[j], bid, smem); else conv_wgrad_pf2_body<CB, 2>(jobs[j], bid, smem);
-    } else {
-      if (mode == 0) conv_bwd_body<CB, 0, 0, 2>(jobs[j], bid, smem); else conv_bwd_body<CB, 2, 0, 2>(jobs[j], bid, smem);
-    }
+    if (mode == 0) conv_bwd_body<CB, 0, 0, 2>(jobs[j], bid, smem); else conv_bwd_body<CB, 2, 0, 2>(jobs[j], bid, smem);
   }
 }
 

@@ -46,12 +46,7 @@ def _nrep() -> int:
 
 DET_WG_PER_MEMBER = 64  # deterministic mode: statistic-producing launches use <= this many workgroups per member
 # Work-split constants of the step plans (each the winner of an A/B in profiles/; the losing variants were deleted)
-DUAL_MAX_POP = 2          # dual (dgrad | wgrad role) backward launches up to this many members per GPU ...
-DUAL_CS = (32, 64)        # ... for these channel widths (C = 16 keeps the fused kernel)
-DUAL_WG = {16: 128, 32: 128, 64: 64}  # wgrad-role workgroups per member of a dual launch
-# small populations: every layer's wgrad deferred past the dgrad chain (1) or run by the dual launches (0: C = 32 / 64
-# dual, C = 16 fused -- the round-2 form, kept as an A/B switch)
-SMALL_DEFER = os.environ.get("DTF_SMALL_DEFER", "1") == "1"
+SMALL_POP_MAX = 2         # "small population": up to this many members per GPU (_StepPlan.small_pop)
 FWD_ITERS_PER_WG = int(os.environ.get("DTF_FWD_ITERS", "4"))  # forward: (image, band) iterations per workgroup (>= FWD_MIN_WG workgroups kept;
 # ... per channel width: C = 64 (the 8x8 stage: one band per image) at 2 -- pop 8 3.006 -> 2.989 ms, 512 workgroups of
 # 2 images instead of 256 of 4 (1: +1.2 %; C = 32 at 2: +0.5 %; profiles/r6_fwd_iters_per_width_ab.log)
@@ -60,9 +55,8 @@ FWD_ITERS_C = {64: 2}
 # ResNet-110 -0.4 %), unchanged at pop <= 4 (a flat 8 cost pop 4 +3 %: 256 workgroups; profiles/r6_fwd_iters16_ab.log)
 FWD_WG_TARGET = {16: int(os.environ.get("DTF_FWD_WG16", "512"))}
 FWD_ITERS_C.update({c: int(os.environ["DTF_FWD_ITERS%d" % c]) for c in (16, 32, 64) if "DTF_FWD_ITERS%d" % c in os.environ})
-FWD_MIN_WG = 256          # 512 for up to DUAL_MAX_POP members: pop 1 1.059 -> 1.055, pop 2 1.427 -> 1.398 ms)
+FWD_MIN_WG = 256          # 512 for up to SMALL_POP_MAX members: pop 1 1.059 -> 1.055, pop 2 1.427 -> 1.398 ms)
 FWD_MIN_WG_SMALL = 512
-FWD_RESIDENT = int(os.environ.get("DTF_FWD_RESIDENT", "0"))  # stride-1 forward: one round of resident workgroups
 HEAD_ITEMS = 512          # head / GAP+dense+CE work items
 WGRAD_WG_PER_MEMBER = 128  # standalone wgrad launches: workgroups per member (bounds the dW partial traffic)
 DENSE_REDUCE_BLOCKS = 256  # slab_reduce_all, dense jobs: max 32-element blocks per job
@@ -114,26 +108,12 @@ def _lib_knob(name):
 
 PIGGYBACK_MAX_WG = 3000   # slab reductions ride on the next backward launch when they add <= this many workgroups
 DEFER_WG = {16: 64, 32: 32, 64: 16}  # deferred wgrad (small populations): workgroups per member and layer
-# deferred wgrad launches issued on a side stream (a parallel branch of the step graph) as soon as a stage's layers
-# -- or OVERLAP_CHUNK of them -- are queued, so they run under the serial dgrad chain of the earlier stages instead
-# of as a tail after it.  Off by default: the two-branch step graph measured SLOWER (pop 1: 1.051 -> 1.272 ms, stage
-# chunks 1.394 ms; pop 2: 1.389 -> 1.577 ms; profiles/r4_wg_overlap_ab.log) -- the branch's cross-stream
-# dependencies cost more than the idle CUs it fills
-WG_OVERLAP = os.environ.get("DTF_WG_OVERLAP", "0") == "1"  # measured slower: profiles/r4_wg_overlap_ab.log
-OVERLAP_CHUNK = int(os.environ.get("DTF_WG_OVERLAP_CHUNK", "0"))  # 0: stage boundaries only
 DEFER_MID_POP = int(os.environ.get("DTF_DEFER_MID_POP", "4"))  # up to this many members: defer the wgrad of DEFER_MID_CS ...
 DEFER_MID_CS = (32, 64)
 DEFER_LARGE_CS = (64,)    # larger populations defer the wgrad of these channel widths only ...
 DEFER_LARGE_WG = {16: 16, 32: int(os.environ.get("DTF_DEFER32_WG", "8")),
                   64: int(os.environ.get("DTF_DEFER64_WG", "8"))}  # ... with this many workgroups per member and layer
-DEFER_ATOMIC = os.environ.get("DTF_DEFER_ATOMIC", "0") == "1"  # deferred wgrad jobs: fp32 atomics instead of dW slabs
-DEFER_ATOMIC_CS = tuple(int(c) for c in os.environ.get("DTF_DEFER_ATOMIC_CS", "16,32,64").split(",") if c)
 V1_CHAIN_BN = os.environ.get("DTF_V1_CHAIN_BN", "1") == "1"  # v1: BN_b backward sums in the next conv_a epilogue
-# small populations: each stage's run of stride-1 forward convs in one persistent launch with a software grid
-# barrier between layers instead of a kernel boundary (conv_fwd_s1_persist_kernel); up to PERSIST_MAX_POP members
-PERSIST_FWD = os.environ.get("DTF_PERSIST_FWD", "0") == "1"
-PERSIST_MAX_POP = int(os.environ.get("DTF_PERSIST_MAX_POP", "2"))
-PERSIST_FENCE = int(os.environ.get("DTF_PERSIST_FENCE", "0"))  # conv.hip persist_barrier fence bits
 HALF_BANDS_MAX_IMGS = 128  # C = 64 stage (8x8): 4-row half-image bands for the forward / dgrad launches up to this many
 #                            images per step (one member: whole-image items left half the CUs idle; pop 2 and the
 #                            C = 32 stage are slower with half bands: profiles/r3_half_bands_ab.log)
@@ -236,11 +216,8 @@ def _register():
     ops.register("dtf_conv_fwd_s1", [P(ConvArgs), c_int, c_int, c_int, c_int, c_int, c_int, c_void_p])
     ops.register("dtf_dw_slab_reduce", [c_void_p, c_void_p, c_int, c_void_p, c_long, c_long, c_int, c_void_p])
     ops.register("dtf_conv_bwd_fused", [P(ConvArgs), c_int, c_int, c_int, c_int, c_int, c_void_p])
-    ops.register("dtf_conv_bwd_dual", [P(ConvArgs), P(ConvArgs), c_int, c_int, c_int, c_int, c_int, c_void_p])
     ops.register("dtf_conv_bwd_dg", [P(ConvArgs), c_int, c_int, c_int, c_int, c_int, c_int, c_void_p])
     ops.register("dtf_conv_wgrad_all", [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p])
-    ops.register("dtf_conv_fwd_s1_persist", [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p,
-                                             c_void_p, c_int, c_int, c_void_p])
     ops.register("dtf_slab_reduce_all", [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_long, c_void_p])
     ops.register("dtf_slab_job_size", [])
     ops.register("dtf_dense_job_size", [])
@@ -412,12 +389,6 @@ class HipResNetBackend(HipBackend):
         self.correct = self.zbuf[nst + cap:]
 
     # --- engine hooks --------------------------------------------------------------
-    def persist_failures(self) -> int:
-        """Software grid barriers of the persistent forward segments that timed out (their step is wrong; 0 on a
-        healthy run: every workgroup of such a launch is co-resident by construction).  Reads the device."""
-        t = getattr(self, "persist_fail", None)
-        return 0 if t is None else int(t.item())
-
     def on_params_changed(self, slots):
         pass  # weight_prep runs at the start of every step (inside the graph)
 
@@ -532,7 +503,7 @@ class _StepPlan:
         self.sizes = sizes
         self._wgen = []
         self.eval = bool(eval_mode)
-        self.persist_fwd = False  # (training plans of small populations may enable it below)
+        self._grab = None  # a list while the launches of a combined multi-role launch are collected (_add)
         dev = be.dev
         L = be.L
         prog = L.prog
@@ -631,28 +602,21 @@ class _StepPlan:
         self.dfeat = torch.zeros(N, cfg.final_size, dtype=torch.float32, device=dev)
         self._work_cache = {}
         self._uniform_geo = {}
-        # Dual backward (small populations, <= DUAL_MAX_POP members): each stride-1 C = 32 / 64 conv's dgrad and wgrad
-        # run as two workgroup roles of ONE launch (conv_bwd_dual_kernel); the layer costs max(dgrad, wgrad) instead
-        # of their sum while the population leaves CUs idle (C = 16 keeps the fused kernel: its single-band work
-        # items already fill the GPU; profiles/r2_dual_pop1_breakdown.txt)
+        # Small population (<= SMALL_POP_MAX members of a v2 net on the GPU, release build): the members leave CUs
+        # idle, so every dgrad-role workgroup takes a single (image, band) iteration and every width defers its wgrad
         # (the deterministic build never switches kernel families with the population size: a member's reduction
         # order must not depend on how many members share its plan -- placement invariance, _work_iters)
-        self.dual = dev.type == "cuda" and cfg.version == 2 and len(slots) <= DUAL_MAX_POP and not be.det
-        # Deferred weight gradients (the same small populations): each stride-1 layer's backward launch runs only
-        # its dgrad role -- the critical path, serialised by the BatchNorm statistics -- and the wgrad work of all
-        # those layers runs afterwards in two wide launches (conv_wgrad_all_kernel: widths 64 + 32, width 16).
-        # Their dY / x operands stay alive for the whole backward (per-block buffers instead of ping-pong ones).
-        self.defer_wg = self.dual and SMALL_DEFER
-        self.persist_fwd = (PERSIST_FWD and dev.type == "cuda" and len(slots) <= PERSIST_MAX_POP
-                            and not self.be.det and not self.eval)
-        self.overlap_wg = self.defer_wg and WG_OVERLAP and dev.type == "cuda"
-        # channel widths whose stride-1 wgrad is deferred: every width at small populations; up to 4 members C = 32
-        # and 64, at larger ones the C = 64 layers only (1 workgroup per CU of the fused kernel left the MFMA pipe
-        # idle, and its 147 KB dW slab per workgroup cost more than re-reading dY / x once in the wide wgrad
-        # launch; profiles/r3_defer_ab.log)
         v2gpu = dev.type == "cuda" and cfg.version == 2
+        self.small_pop = v2gpu and len(slots) <= SMALL_POP_MAX and not be.det
+        # Deferred weight gradients: a stride-1 layer of one of these channel widths launches only its dgrad role --
+        # the critical path, serialised by the BatchNorm statistics -- and the wgrad work of all those layers runs
+        # afterwards in two wide launches (conv_wgrad_all_kernel: widths 64 + 32, width 16).  Their dY / x operands
+        # stay alive for the whole backward (per-block buffers instead of ping-pong ones).  Every width at small
+        # populations; up to 4 members C = 32 and 64, at larger ones the C = 64 layers only (1 workgroup per CU of
+        # the fused kernel left the MFMA pipe idle, and its 147 KB dW slab per workgroup cost more than re-reading
+        # dY / x once in the wide wgrad launch; profiles/r3_defer_ab.log)
         large = DEFER_MID_CS if (len(slots) <= DEFER_MID_POP and not be.det) else DEFER_LARGE_CS
-        self.defer_cs = {16, 32, 64} if self.defer_wg else (set(large) if v2gpu and not self.dual else set())
+        self.defer_cs = {16, 32, 64} if self.small_pop else (set(large) if v2gpu else set())
         self._wg_jobs = {}  # (C, wgrad dY mode) -> [(ConvArgs, work table, grad offset)]
         self.launches = []
         self._pending_slab = None  # (slab ptr, reduce table, C, grad offset) of the last fused launch
@@ -834,56 +798,10 @@ class _StepPlan:
         return b.gamma_off, b.beta_off
 
     def _add(self, fn, *args):
-        if getattr(self, "_pseg", None):
-            self._flush_pseg()  # a pending persistent forward segment precedes every other launch
-        if getattr(self, "_grab", None) is not None:
+        if self._grab is not None:
             self._grab.append((fn, args))  # collected for a combined multi-role launch
             return
         self.launches.append((fn, args))
-
-    def _pseg_add(self, a, cin, mode, resid, rows, nwg, lds):
-        """Queue a conv_fwd_s1 launch into the pending persistent segment (same C / bands / workgroup count)."""
-        seg = getattr(self, "_pseg", None)
-        if seg and (seg[0][1], seg[0][4], seg[0][5]) != (cin, rows, nwg):
-            self._flush_pseg()
-            seg = None
-        if not seg:
-            self._pseg = seg = []
-        seg.append((a, cin, mode, resid, rows, nwg, lds))
-
-    def _flush_pseg(self):
-        """Emit the pending segment: one persistent launch (2+ layers whose workgroups are all co-resident), else
-        the ordinary per-layer launches."""
-        seg, self._pseg = self._pseg, None
-        lib = ops.lib()
-        if not seg:
-            return
-        cin, rows, nwg = seg[0][1], seg[0][4], seg[0][5]
-        lds = max(t[6] for t in seg)
-        be = self.be
-        if len(seg) >= 2:
-            if getattr(be, "persist_fail", None) is None:
-                be.persist_fail = torch.zeros(1, dtype=torch.int32, device=be.dev)
-            # this segment's own arrival-flag words (conv.hip persist_barrier: [64 + b]): every launch of the segment
-            # has the same workgroup count and barrier count, so its flags stay in lockstep across replays
-            bar = torch.zeros(64 + 1024, dtype=torch.int32, device=be.dev)
-            self._keep(bar)
-            arr = (ConvArgs * len(seg))(*[t[0] for t in seg])
-            tbl = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(be.dev)
-            kinds = torch.tensor([0 if t[2] == 0 else (2 if t[3] else 1) for t in seg], dtype=torch.int32,
-                                 device=be.dev)
-            ok = lib.dtf_conv_fwd_s1_persist(_p(tbl), _p(kinds), len(seg), cin, rows, nwg, lds, _p(bar),
-                                             _p(be.persist_fail), PERSIST_FENCE, 1, None)
-            if ok == 1 and nwg <= 1024 and all(t[2] != 0 or rows == 8 for t in seg):
-                self._keep(tbl)
-                self._keep(kinds)
-                self.launches.append((lib.dtf_conv_fwd_s1_persist,
-                                      (_p(tbl), _p(kinds), len(seg), cin, rows, nwg, lds, _p(bar),
-                                       _p(be.persist_fail), PERSIST_FENCE, 0)))
-                self.persist_segments = getattr(self, "persist_segments", 0) + 1
-                return
-        for a, cin, mode, resid, rows, nwg, lds in seg:
-            self.launches.append((lib.dtf_conv_fwd_s1, (ctypes.byref(a), cin, mode, int(resid), rows, nwg, lds)))
 
     def _conv_fwd(self, ci, x, y, stats_bn, in_bn, res=None):
         be, L = self.be, self.be.L
@@ -903,14 +821,11 @@ class _StepPlan:
         if s1 and cin == 64 and self.N <= HALF_BANDS_MAX_IMGS and in_bn is not None and not be.det:
             rows = 4  # conv_fwd_s1_kernel<64, ., ., 4>
         bands = Ho // rows
-        lo = FWD_MIN_WG_SMALL if len(self.slots) <= DUAL_MAX_POP else FWD_MIN_WG
+        lo = FWD_MIN_WG_SMALL if len(self.slots) <= SMALL_POP_MAX else FWD_MIN_WG
         iters = FWD_ITERS_C.get(cin, FWD_ITERS_PER_WG)
         if cin in FWD_WG_TARGET:  # no more than this many workgroups: longer ones once the population allows
             iters = max(iters, min(8, self.N * bands // FWD_WG_TARGET[cin]))  # (16 at 256 workgroups: +2.4 %)
         n_wg = self._n_wg_iters(self.N * bands, per_wg=iters, lo=lo, hi=max(1024, self.N * bands // iters))
-        if FWD_RESIDENT and s1 and len(self.slots) > DUAL_MAX_POP:
-            # conv_fwd_s1_kernel occupancy: 4 WGs / CU (C <= 32), 3 (C = 64)
-            n_wg = self._det_cap(min(self.N * bands, _n_cu() * (4 if cin <= 32 else 3)))
         work = self._work_iters(bands, n_wg)
         a = self._base_args()
         a.x, a.y, a.res = _p(x), _p(y), _p(res)
@@ -932,11 +847,7 @@ class _StepPlan:
             self._set_uniform(a, work)
             a.cin_real = self._stamp_row("fwd", "fwd_s1 C=%d in=%d res=%d" % (cin, mode, res is not None))  # launch ordinal for DTF_STAMP diagnostic builds (unused otherwise)
             lds = 1280 + 2 * ((rows_in * _wpitch(cin) * _cpad_fwd(cin) + 8 + 63) // 64 * 64) * 2
-            if self.persist_fwd and getattr(self, "_grab", None) is None:
-                self._pseg_add(a, cin, mode, res is not None, rows, work.shape[0], lds)
-            else:
-                self._add(lib.dtf_conv_fwd_s1, ctypes.byref(a), cin, mode, int(res is not None), rows,
-                          work.shape[0], lds)
+            self._add(lib.dtf_conv_fwd_s1, ctypes.byref(a), cin, mode, int(res is not None), rows, work.shape[0], lds)
         else:
             self._add(lib.dtf_conv_fwd, ctypes.byref(a), cin, c.cout, c.stride, c.k, mode, int(res is not None),
                       int(stats_bn is not None), work.shape[0], lds)
@@ -1076,36 +987,22 @@ class _StepPlan:
         for t in (dy, dy2, dy3, dy_out, dz_out, x, res):
             assert t is None or tuple(t.shape) == (self.N, H, H, C), (t.shape, C, H)
         bands = H // rows
-        if (self.dual and (C in DUAL_CS or self.defer_wg)) or C in self.defer_cs:
-            # the dual / deferred launches have no epilogue for a chained BN's backward sums: a caller that marked
-            # the previous block as chained (v1 _build_v1) would silently lose them
-            assert chain_bn is None, "chain_bn needs the fused launch (dual / deferred paths are v2-only)"
-            return self._conv_bwd_dual(ci, c, C, H, rows, bands, dy, dz_out, x, mode_dy, dy2, dy_bn, x_bn, res,
-                                       ident_x, dy3, dy_out)
+        if C in self.defer_cs:
+            # the deferred launches have no epilogue for a chained BN's backward sums: a caller that marked the
+            # previous block as chained (v1 _build_v1) would silently lose them
+            assert chain_bn is None, "chain_bn needs the fused launch (the deferred path is v2-only)"
+            return self._conv_bwd_deferred(ci, rows, dy, dz_out, x, mode_dy, dy2, dy_bn, x_bn, res, ident_x, dy3,
+                                           dy_out)
         n_wg = self._fused_nwg(C, bands, mode_dy)
         work = self._work_iters(bands, n_wg)
-        a = self._base_args()
-        a.x, a.x2, a.y, a.xm, a.res = _p(dy), _p(dy2), _p(dz_out), _p(x), _p(res)
-        a.x3, a.xout = _p(dy3), _p(dy_out)
-        a.w, a.w_off = _p(be.wd), L.dgr_off[ci]
-        a.work = _p(work)
-        a.g_off = c.off
-        a.n_main = work.shape[0]
-        self._set_uniform(a, work)
-        if dy_bn is not None:
-            a.in_gamma, a.in_beta = self._bn(dy_bn)
-            a.st_in, a.st_in_b = _p(be.st_f(dy_bn)), _p(be.st_b(dy_bn))
-        if not ident_x:
-            a.ep_gamma, a.ep_beta = self._bn(x_bn)
-            a.st_ep = _p(be.st_f(x_bn))
-            a.st_out = _p(be.st_b(x_bn))
+        a = self._bwd_args(ci, work, rows, dy, dy2, dy3, x, dy_bn, None if ident_x else x_bn,
+                           dgrad=(dz_out, res, dy_out))
         if chain_bn is not None:
             assert ident_x and mode_dy == 2 and tuple(chain_h.shape) == (self.N, H, H, C)
             a.x3 = _p(chain_h)
             a.ep_gamma, a.ep_beta = self._bn(chain_bn)
             a.st_ep = _p(self._st_r(chain_bn))
             a.st_out = _p(be.st_b(chain_bn))
-        a.Hi, a.Wi, a.Ho, a.Wo, a.rows = H, H, H, H, rows
         tsz = ((rows + 2) * _wpitch(C) * _cpad(C) + 8 + 63) // 64 * 64
         raw = C >= 64  # must match conv.hip RAWX
         nbuf = 4  # double-buffered size even when conv.hip single-buffers (SB): C = 16 still fits 3 WGs per CU
@@ -1140,127 +1037,82 @@ class _StepPlan:
         else:
             self._pending_slab = (a.slab, red, C, c.off)
 
-    def _conv_bwd_dual(self, ci, c, C, H, rows, bands, dy, dz_out, x, mode_dy, dy2, dy_bn, x_bn, res, ident_x, dy3,
-                       dy_out):
-        """Dual backward of a stride-1 C->C conv (conv_bwd_dual_kernel): dgrad-role workgroups (one (image, band)
-        iteration each by default: the critical path) and wgrad-role workgroups (DUAL_WG[C] per member, each
-        over a run of iterations, writing a dW slab) in one launch; both stage the same transformed dY.  The
-        slabs are reduced by the trailing workgroups of the next backward launch (or a standalone reduction)."""
+    def _bwd_args(self, ci, work, rows, dy, dy2, dy3, x, dy_bn, x_bn, dgrad=None):
+        """ConvArgs of a stride-1 backward launch or job over ``work``: the dY operands (BN ``dy_bn``'s backward
+        transform on load), the layer input ``x`` with the parameters and forward statistics of its BN ``x_bn``
+        (None: identity), the gradient offset.  ``dgrad`` = (dz_out, res, dy_out): also the dgrad side -- the
+        IHWO weights, the output tensors and where the epilogue adds BN ``x_bn``'s backward sums."""
         be, L = self.be, self.be.L
-        lib = ops.lib()
-        tsz = ((rows + 2) * _wpitch(C) * _cpad(C) + 8 + 63) // 64 * 64
-        epi = int(res is not None) | (2 if ident_x else 0)
-        # ---- dgrad role: one (image, band) iteration per workgroup (larger populations: DG_ITERS_LARGE); the
-        # deferred-wgrad dgrad launch of the C = 64 stage takes half-image bands at small populations
-        rows_dg = 4 if (C == 64 and C in self.defer_cs and self.N <= HALF_BANDS_MAX_IMGS and not be.det) else rows
-        bands_dg = H // rows_dg
-        n_dg = max(1, self.N * bands_dg)
-        if not self.dual:
-            n_dg = min(n_dg, max(DG_MIN_WG, -(-n_dg // DG_ITERS_LARGE)))
-        work = self._work_iters(bands_dg, self._det_cap(n_dg))
+        H = x.shape[1]
         a = self._base_args()
-        a.x, a.x2, a.y, a.xm, a.res = _p(dy), _p(dy2), _p(dz_out), _p(x), _p(res)
-        a.x3, a.xout = _p(dy3), _p(dy_out if mode_dy >= 2 else None)
-        a.w, a.w_off = _p(be.wd), L.dgr_off[ci]
+        a.x, a.x2, a.x3, a.xm = _p(dy), _p(dy2), _p(dy3), _p(x)
         a.work = _p(work)
-        a.g_off = c.off
+        a.g_off = L.prog.convs[ci].off
         a.n_main = work.shape[0]
         self._set_uniform(a, work)
         if dy_bn is not None:
             a.in_gamma, a.in_beta = self._bn(dy_bn)
             a.st_in, a.st_in_b = _p(be.st_f(dy_bn)), _p(be.st_b(dy_bn))
-        if not ident_x:
+        if x_bn is not None:
             a.ep_gamma, a.ep_beta = self._bn(x_bn)
             a.st_ep = _p(be.st_f(x_bn))
-            a.st_out = _p(be.st_b(x_bn))
-        a.Hi, a.Wi, a.Ho, a.Wo, a.rows = H, H, H, H, rows_dg
-        a.cin_real = self._stamp_row("fused", "fused-dg C=%d mdy=%d epi=%d" % (C, mode_dy, epi))
-        # ---- wgrad role (same staging of dY / X; own work split)
-        wwork = self._work_iters(bands, max(1, min(self.N * bands, DUAL_WG[C] * len(self.slots))))
-        b = self._base_args()
-        b.x, b.x2, b.x3, b.xm = _p(dy), _p(dy2), _p(dy3), _p(x)
-        b.work = _p(wwork)
-        b.g_off = c.off
-        b.n_main = wwork.shape[0]
-        self._set_uniform(b, wwork)
-        if dy_bn is not None:
-            b.in_gamma, b.in_beta = self._bn(dy_bn)
-            b.st_in, b.st_in_b = _p(be.st_f(dy_bn)), _p(be.st_b(dy_bn))
-        if not ident_x:
-            b.ep_gamma, b.ep_beta = self._bn(x_bn)
-            b.st_ep = _p(be.st_f(x_bn))
-        b.Hi, b.Wi, b.Ho, b.Wo, b.rows = H, H, H, H, rows
-        b.cin_real = self._stamp_row("fused", "fused-wg C=%d mdy=%d epi=%d" % (C, mode_dy, epi))
-        if C in self.defer_cs:
-            return self._defer_wgrad(ci, c, C, H, rows, bands, a, b, dy, x, mode_dy, dy2, dy_bn, x_bn, dy_out,
-                                     tsz, epi)
-        b.slab = _p(self._layer_slab(wwork.shape[0] * self._slab_elems(C)))
-        # ---- trailing reduction of the previous backward launch's slabs
-        n_red = 0
-        pend = self._pending_slab
-        if pend is not None and self._piggyback(pend):
-            buf, red, rc, goff = pend
-            a.rslab, a.rtab, a.r_c, a.r_goff = buf, _p(red), rc, goff
-            a.r_nblk = self._reduce_wgs(rc)
-            n_red = a.r_nblk * red.shape[0]
-            self._pending_slab = None
-        else:
-            self._flush_slab()
-        self._keep(a)
-        self._keep(b)
-        lds = 2304 + 4 * tsz * 2  # the wgrad role's dY + X tiles (double-buffered); the dgrad role uses half
-        self._add(lib.dtf_conv_bwd_dual, ctypes.byref(a), ctypes.byref(b), C, mode_dy, epi,
-                  a.n_main + b.n_main + n_red, lds)
-        if C == 64:
-            self._deferred.append((b.slab, self._slab_table(wwork), c.off, 64))
-        else:
-            self._pending_slab = (b.slab, self._slab_table(wwork), C, c.off)
+        if dgrad is not None:
+            dz_out, res, dy_out = dgrad
+            a.y, a.res, a.xout = _p(dz_out), _p(res), _p(dy_out)
+            a.w, a.w_off = _p(be.wd), L.dgr_off[ci]
+            if x_bn is not None:
+                a.st_out = _p(be.st_b(x_bn))
+        a.Hi, a.Wi, a.Ho, a.Wo, a.rows = H, H, H, H, rows
+        return a
 
-    def _defer_wgrad(self, ci, c, C, H, rows, bands, a, b, dy, x, mode_dy, dy2, dy_bn, x_bn, dy_out, tsz, epi):
-        """Deferred-wgrad form of a dual launch: the launch holds the dgrad role only; the wgrad job (the role's
-        arguments with its own work split) is queued for conv_wgrad_all_kernel.  Its dY operand: the dY the
-        dgrad role materialises (``dy_out``) or the plain incoming gradient (mode 0), read as-is; else (conv_a)
-        BN2-backward(dz2, h) recomputed while staging, as the dgrad role does."""
-        lib = ops.lib()
+    def _conv_bwd_deferred(self, ci, rows, dy, dz_out, x, mode_dy, dy2, dy_bn, x_bn, res, ident_x, dy3, dy_out):
+        """Backward of a stride-1 C->C conv whose wgrad is deferred (C in defer_cs): the launch runs the dgrad role
+        alone (conv_bwd_dg_kernel) and the layer's wgrad job -- its own work split and dW slab -- is queued for
+        conv_wgrad_all_kernel (_emit_deferred_wgrad).  The job's dY operand: the dY the dgrad role materialises
+        (``dy_out``) or the plain incoming gradient (mode 0), read as-is; else (conv_a) BN2-backward(dz2, h)
+        recomputed while staging, as the dgrad role does."""
+        be = self.be
+        c = be.L.prog.convs[ci]
+        C, H = c.cin, x.shape[1]
+        epi = int(res is not None) | (2 if ident_x else 0)
+        x_bn = None if ident_x else x_bn
+        # ---- dgrad role: one (image, band) iteration per workgroup (larger populations: DG_ITERS_LARGE); the
+        # C = 64 stage takes half-image bands while the step has few images
+        rows_dg = 4 if (C == 64 and self.N <= HALF_BANDS_MAX_IMGS and not be.det) else rows
+        n_dg = max(1, self.N * (H // rows_dg))
+        if not self.small_pop:
+            n_dg = min(n_dg, max(DG_MIN_WG, -(-n_dg // DG_ITERS_LARGE)))
+        work = self._work_iters(H // rows_dg, self._det_cap(n_dg))
+        a = self._bwd_args(ci, work, rows_dg, dy, dy2, dy3, x, dy_bn, x_bn,
+                           dgrad=(dz_out, res, dy_out if mode_dy >= 2 else None))
+        a.cin_real = self._stamp_row("fused", "fused-dg C=%d mdy=%d epi=%d" % (C, mode_dy, epi))
+        tsz = ((rows_dg + 2) * _wpitch(C) * _cpad(C) + 8 + 63) // 64 * 64
+        self._add(ops.lib().dtf_conv_bwd_dg, ctypes.byref(a), C, mode_dy, epi, rows_dg, a.n_main, 2304 + 2 * tsz * 2)
         self._keep(a)
-        tsz_dg = ((a.rows + 2) * _wpitch(C) * _cpad(C) + 8 + 63) // 64 * 64
-        self._add(lib.dtf_conv_bwd_dg, ctypes.byref(a), C, mode_dy, epi, a.rows, a.n_main, 2304 + 2 * tsz_dg * 2)
-        w = self._base_args()
-        ctypes.memmove(ctypes.addressof(w), ctypes.addressof(b), ctypes.sizeof(ConvArgs))
+        # ---- wgrad job (the same staging of dY / x over 8-row bands)
         if dy_out is not None or mode_dy == 0:
-            wmode = 0
-            w.x, w.x2, w.x3 = _p(dy_out if dy_out is not None else dy), None, None
-            w.in_gamma = w.in_beta = 0
-            w.st_in = w.st_in_b = None
+            wmode, dy, dy2, dy_bn = 0, dy_out if dy_out is not None else dy, None, None
         else:
             wmode = 2
             assert mode_dy == 2 and dy2 is not None and dy_bn is not None
-        per = DEFER_WG[C] if self.defer_wg else DEFER_LARGE_WG[C]
+        per = DEFER_WG[C] if self.small_pop else DEFER_LARGE_WG[C]
+        bands = H // rows
         wwork = self._work_iters(bands, max(1, min(self.N * bands, per * len(self.slots))), det_per=per)
-        w.work = _p(wwork)
-        w.n_main = wwork.shape[0]
-        self._set_uniform(w, wwork)
-        # DEFER_ATOMIC (release build): the job's workgroups add their dW partials straight into the gradient rows
-        # (fp32 atomics, a handful of workgroups per address) instead of writing slabs for slab_reduce_all
-        atomic = DEFER_ATOMIC and not self.be.det and C in DEFER_ATOMIC_CS
-        w.slab = None if atomic else _p(self._layer_slab(wwork.shape[0] * self._slab_elems(C)))
+        w = self._bwd_args(ci, wwork, rows, dy, dy2, None, x, dy_bn, x_bn)
+        w.slab = _p(self._layer_slab(wwork.shape[0] * self._slab_elems(C)))
+        self._stamp_row("fused", "fused-wg C=%d mdy=%d epi=%d" % (C, mode_dy, epi))  # (row kept; the job stamps none)
         w.cin_real = -1
         self._wg_jobs.setdefault((C, wmode), []).append((w, wwork, c.off))
 
-    def _emit_deferred_wgrad(self, only_c=None, side=False):
+    def _emit_deferred_wgrad(self):
         """Every queued layer's wgrad job in two launches (conv_wgrad_all_kernel: widths 64 + 32 -- one wave per SIMD
         -- and width 16, kept apart at its higher occupancy); their slabs join the reduction of _flush_deferred.
-        One launch per (C, dY mode) measured 18 us slower at pop 1 (profiles/r3_merged_launches_ab.log).
-        ``only_c``: just the jobs of that width; ``side``: on the side stream (a parallel graph branch, joined before
-        the slab reduction)."""
+        One launch per (C, dY mode) measured 18 us slower at pop 1 (profiles/r3_merged_launches_ab.log)."""
         lib = ops.lib()
-        if side and any(C == only_c or only_c is None for (C, _) in self._wg_jobs):
-            self._add("fork", None)
-            self._forked = True
         for cset, widths in ((0, (64, 32)), (1, (16,))):  # must match dtf_conv_wgrad_all's instantiations
             arr_l, wmap, lds = [], [], 0
             for (C, wmode), jobs in sorted(self._wg_jobs.items(), key=lambda kv: (-kv[0][0], -kv[0][1])):
-                if C not in widths or (only_c is not None and C != only_c):
+                if C not in widths:
                     continue
                 tsz = ((8 + 2) * _wpitch(C) * _cpad(C) + 8 + 63) // 64 * 64
                 lds = max(lds, 2304 + 4 * tsz * 2)
@@ -1268,8 +1120,7 @@ class _StepPlan:
                     j = len(arr_l)
                     arr_l.append(w)
                     wmap += [(j, k, C, wmode) for k in range(w.n_main)]
-                    if w.slab:  # (None: the job accumulates with atomics, DEFER_ATOMIC)
-                        self._deferred.append((w.slab, self._slab_table(work), goff, C))
+                    self._deferred.append((w.slab, self._slab_table(work), goff, C))
             if not arr_l:
                 continue
             arr = (ConvArgs * len(arr_l))(*arr_l)
@@ -1278,20 +1129,7 @@ class _StepPlan:
             self._keep(jt)
             self._keep(mt)
             self._add(lib.dtf_conv_wgrad_all, _p(jt), _p(mt), len(wmap), cset, lds)
-        if side and getattr(self, "_forked", False):
-            self._add("endfork", None)
-        self._wg_jobs = {k: v for k, v in self._wg_jobs.items() if only_c is not None and k[0] != only_c}
-
-    def _maybe_overlap_wgrad(self, i):
-        """After block i's backward: issue the queued deferred wgrad jobs of its width on the side stream when the
-        next block to process has another width (stage boundary) or OVERLAP_CHUNK jobs are queued."""
-        if not (self.overlap_wg and self._wg_jobs):
-            return
-        C = self.hs[i].shape[3]
-        nxt = self.hs[i - 1].shape[3] if i > 0 else None
-        queued = sum(len(v) for (c, _), v in self._wg_jobs.items() if c == C)
-        if nxt != C or (OVERLAP_CHUNK and queued >= OVERLAP_CHUNK):
-            self._emit_deferred_wgrad(only_c=C, side=True)
+        self._wg_jobs = {}
 
     def _fresh_like(self, t):
         u = torch.empty_like(t)
@@ -1542,12 +1380,9 @@ class _StepPlan:
             else:
                 self._bn_bwd_apply(Tin["dz1"], x, add, g_next, bn1)
             g_cur = g_next
-            self._maybe_overlap_wgrad(i)
         # stem wgrad (input = padded image, real channels 3)
         self._conv_wgrad(prog.stem, self.xin16, g_cur, mode_x=0, mode_dy=0, cin_real=cfg.in_channels)
         self._emit_deferred_wgrad()
-        if getattr(self, "_forked", False):
-            self._add("join", None)  # the side-stream wgrad branch ends before the slab reduction
         # BN parameter gradients from the backward reductions
         self._flush_slab()
         self._flush_deferred()
@@ -1828,23 +1663,8 @@ class _StepPlan:
 
     def _run_eager(self):
         e = self.e
-        main = torch.cuda.current_stream() if self.be.dev.type == "cuda" else None
-        target = None  # None: the current stream; else the side stream of a fork
         for fn, args in self.launches:
-            if fn == "fork":  # the side stream waits for everything issued so far on the main stream
-                if getattr(self, "_side", None) is None:
-                    self._side = torch.cuda.Stream(device=self.be.dev)
-                self._side.wait_stream(main)
-                target = self._side
-            elif fn == "endfork":
-                target = None
-            elif fn == "join":
-                main.wait_stream(self._side)
-            elif target is not None:
-                err = fn(*args, target.cuda_stream)
-                if err != 0:
-                    raise RuntimeError("kernel launch %s failed with %d" % (getattr(fn, "__name__", fn), err))
-            elif fn == "augment":
+            if fn == "augment":
                 # crops keyed per member (its step counter + dataset row): placement-invariant (data.hip)
                 ops.augment_cifar(self.src.train_x, self.src.train_y, self.idx, self.rng, True, out16=self.xin16,
                                   lab32=self.labels, member_keys=(self.img_slot, e.state, e.S, 3 * e.Pp + e.R))

@@ -216,7 +216,7 @@ __host__ __device__ constexpr int cpad() {
   return C == 16 ? 16 : C == 32 ? 48 : C == 64 ? 80 : C + 8;
 }
 
-// LDS row pitch (pixels) of the stage kernels' [RT][WP][CP] tiles (conv_fwd_s1, fused / dual backward).  C = 64
+// LDS row pitch (pixels) of the stage kernels' [RT][WP][CP] tiles (conv_fwd_s1, fused / dgrad-role backward).  C = 64
 // (W = 8): a 16-pixel MFMA operand gather spans two image rows; with a 16-pixel row pitch the two rows land
 // in disjoint bank halves of the ds_read_b128 lane groups (4 instead of 8 cycles per gather, tools/lds_banks.py;
 // the extra 6 columns are never staged).  Measured: no step-time change at pop 1 / pop 8 (these kernels wait on
@@ -1256,94 +1256,6 @@ __global__ __launch_bounds__(256) void conv_fwd_s1_kernel(ConvArgs a) {
   conv_fwd_s1_body<C, MODE_IN, RESID, ROWS>(a, (int)blockIdx.x, smem);
 }
 
-// ------------------------------------------------------------------ persistent forward segment (small populations)
-// A run of conv_fwd_s1 layers of one stage (stem / conv_a / conv_b, the same C and band geometry and the same
-// workgroup count) in ONE launch: each workgroup runs its work item of layer l, then a software grid barrier
-// replaces the kernel boundary before layer l + 1 (whose BatchNorm prologue needs layer l's complete statistics).
-// The barrier: release fence (this workgroup's activation stores / statistic atomics visible at agent scope), one
-// arrival atomic on a flat counter, the last arriver resets it and bumps the generation word the others spin on
-// (bounded: a barrier that does not complete within ~50 ms counts a failure and ends the kernel -- the step's
-// result is then wrong and the host reports it -- instead of hanging the GPU), acquire fence (drops this XCD's
-// stale L2 lines of the next layer's inputs).  The host launches it only when every workgroup is co-resident
-// (occupancy check in dtf_conv_fwd_s1_persist).  kinds[l]: 0 stem (identity input), 1 BN+ReLU input, 2 + residual.
-// fence bits: 1 agent release (else only this wave's counters drained), 2 agent acquire (L2 invalidate).
-// bar: [0] generation, [64 + b] arrival flag of workgroup b (generation-stamped: never reset; one bar array per
-// persistent segment).  Arrival is a store to the workgroup's own word -- a single arrival counter (512 serialised
-// same-address atomics) measured ~8 us per barrier; workgroup 0's first wave polls every flag, then publishes the
-// next generation, which the others poll.  (Every workgroup polling all flags itself instead measured slower:
-// profiles/r4_persist_ab.log.)
-__device__ __forceinline__ bool persist_barrier(unsigned* bar, unsigned nwg, unsigned* fail, int fence) {
-  __shared__ int ok;
-  __syncthreads();
-  const unsigned bid = blockIdx.x;
-  const int t = threadIdx.x;
-  unsigned g = 0;
-  if (t < 64) g = __hip_atomic_load(bar, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  if (t == 0) {
-    ok = 1;
-    // Release: activation stores are write-through (st_act8) and the statistics agent-scope atomics, so completing
-    // this workgroup's outstanding memory operations is enough (fence bit 1 adds the agent fence's L2 write-back).
-    // Acquire: every buffer a layer reads was first written inside this launch (distinct activation buffers per
-    // layer; statistics rows read only after their layer) and the L2 was clean at launch, so no stale line exists
-    // (fence bit 2 adds the agent acquire's L2 invalidate).
-    if (fence & 1)
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-    else
-      __builtin_amdgcn_s_waitcnt(0);
-    __hip_atomic_store(bar + 64 + bid, g + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-  if (bid == 0 && t < 64) {
-    bool all = false;
-    for (int it = 0; it < (1 << 20) && !all; ++it) {
-      bool mine = true;
-      for (unsigned w = t; w < nwg; w += 64)
-        mine = mine && __hip_atomic_load(bar + 64 + w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == g + 1;
-      all = __all(mine);
-      if (!all) __builtin_amdgcn_s_sleep(1);
-    }
-    if (t == 0) {
-      if (all) {
-        __hip_atomic_store(bar, g + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      } else {
-        ok = 0;
-        atomicAdd(fail, 1u);
-      }
-    }
-  } else if (t == 0) {
-    bool done = false;
-    for (int it = 0; it < (1 << 20) && !done; ++it) {
-      done = __hip_atomic_load(bar, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != g;
-      if (!done) __builtin_amdgcn_s_sleep(1);
-    }
-    if (!done) {
-      ok = 0;
-      atomicAdd(fail, 1u);
-    }
-  }
-  if (t == 0 && (fence & 2)) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-  __syncthreads();
-  return ok != 0;
-}
-
-template <int C, int ROWS>
-__global__ __launch_bounds__(256) void conv_fwd_s1_persist_kernel(const ConvArgs* __restrict__ layers,
-                                                                  const int* __restrict__ kinds, int nlayers,
-                                                                  unsigned* bar, unsigned* fail, int fence) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int bid = (int)blockIdx.x;
-  for (int l = 0; l < nlayers; ++l) {
-    const int kind = kinds[l];
-    if (kind == 0) {
-      if constexpr (ROWS == 8) conv_fwd_s1_body<C, 0, false, ROWS>(layers[l], bid, smem);
-    } else if (kind == 1) {
-      conv_fwd_s1_body<C, 1, false, ROWS>(layers[l], bid, smem);
-    } else {
-      conv_fwd_s1_body<C, 1, true, ROWS>(layers[l], bid, smem);
-    }
-    if (l + 1 < nlayers && !persist_barrier(bar, gridDim.x, fail, fence)) return;
-  }
-}
-
 // ---------------------------------------------------------------------------------- dgrad
 // dx[iy,ix,ci] = sum_{ky,kx,co} dy[(iy+P-ky)/S, (ix+P-kx)/S, co] * W[co,ky,kx,ci]
 // Weights in IHWO layout: wt[ci][tap][co] (rows of the A operand are ci).
@@ -1821,9 +1733,9 @@ __device__ __forceinline__ void slab_reduce_wg(const float* __restrict__ slab, c
 // a 32-bit lane offset fixed for the workgroup, and the elementwise work uses
 // packed fp32 / bf16 math: the VALU budget per MFMA is what bounds these
 // small-channel layers.
-// ROLE (dual backward of small populations, conv_bwd_dual_kernel): 0 = dgrad + wgrad (fused),
-// 1 = dgrad only (critical path: no X tile, no wgrad; the transformed dY may be materialised via xout for the
-// wgrad), 2 = wgrad only (the wgrad role of a dual launch; no dgrad / stats / xout).
+// ROLE: 0 = dgrad + wgrad (fused), 1 = dgrad only (conv_bwd_dg_kernel, the critical path of a layer whose wgrad is
+// deferred: no X tile, no wgrad; the transformed dY may be materialised via xout for the wgrad), 2 = wgrad only
+// (a deferred layer's job in conv_wgrad_all_kernel; no dgrad / stats / xout).
 // Body of one workgroup; `bid` = the workgroup's index within its role (work item, stats replica, dW slab row).
 template <int C, int MODE_DY, int EPI, int ROLE, int ROWS = 8>
 __device__ __forceinline__ void conv_bwd_body(const ConvArgs& a, const int bid, char* smem) {
@@ -2266,29 +2178,8 @@ __global__ __launch_bounds__(256, FUSED_WAVES(C, MODE_DY)) void conv_bwd_fused_k
   conv_bwd_body<C, MODE_DY, EPI, 0>(a, (int)blockIdx.x, smem);
 }
 
-// Dual backward (engine/hip_resnet.py _conv_bwd_dual): ONE launch whose workgroups take
-// different roles of the same layer -- [0, a.n_main): dgrad role (args a: staging, dgrad MFMAs, mask / stats
-// epilogue, dz out); [a.n_main, + b.n_main): wgrad role (args b: its own work split over the same (image, band)
-// iterations, the same dY / X staging, wgrad MFMAs, dW slab); then the trailing slab reduction of the previous
-// launch (a.r_*).  The two roles run side by side on different CUs, so the layer costs max(dgrad, wgrad) instead
-// of their sum while a small population leaves most CUs idle.
-template <int C, int MODE_DY, int EPI>
-__global__ __launch_bounds__(256, FUSED_WAVES(C, MODE_DY)) void conv_bwd_dual_kernel(ConvArgs a, ConvArgs b) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int bx = (int)blockIdx.x;
-  int na = a.n_main, nb = b.n_main;
-  kpin(na), kpin(nb);  // both role bounds in one scalar round trip
-  if (bx < na) {
-    conv_bwd_body<C, MODE_DY, EPI, 1>(a, bx, smem);
-  } else if (bx < na + nb) {
-    conv_bwd_body<C, MODE_DY, EPI & 2, 2>(b, bx - a.n_main, smem);
-  } else {
-    trailing_reduce(a, bx - a.n_main - b.n_main, smem);
-  }
-}
-
 // dgrad role alone (the backward launch of a layer whose wgrad is deferred to conv_wgrad_all_kernel): without the
-// wgrad role's accumulators the kernel fits two waves per SIMD (the dual kernel is register-capped at one).
+// wgrad role's accumulators the kernel fits two waves per SIMD.
 template <int C, int MODE_DY, int EPI, int ROWS = 8>
 __global__ __launch_bounds__(256, 2) void conv_bwd_dg_kernel(ConvArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -2480,31 +2371,6 @@ DTF_API int dtf_conv_fwd_s1(const ConvArgs* args, int c, int mode, int resid, in
   return -1;
 }
 
-// Persistent forward segment (conv_fwd_s1_persist_kernel): layers = device ConvArgs table, kinds[l] as above.
-// check_only: return 1 if nblocks workgroups of this instantiation are co-resident on the device (0 otherwise)
-// without launching.  Returns -3 (no launch) when they are not: the caller must not rely on the barrier then.
-DTF_API int dtf_conv_fwd_s1_persist(const ConvArgs* layers, const int* kinds, int nlayers, int c, int rows,
-                                    int nblocks, int lds, unsigned* bar, unsigned* fail, int fence,
-                                    int check_only, hipStream_t stream) {
-  if (nblocks <= 0 || nlayers <= 0) return 0;
-  DTF_HOST_CHECK(lds <= 160 * 1024);
-  auto go = [&](auto kern) -> int {
-    int per_cu = 0, dev = 0, ncu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 256, lds) != hipSuccess) return -3;
-    if (hipGetDevice(&dev) != hipSuccess) return -3;
-    if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return -3;
-    if ((long)per_cu * ncu < nblocks) return check_only ? 0 : -3;
-    if (check_only) return 1;
-    hipLaunchKernelGGL(kern, dim3(nblocks), dim3(256), lds, stream, layers, kinds, nlayers, bar, fail, fence);
-    return DTF_CHECK_LAUNCH();
-  };
-  if (rows == 8 && c == 16) return go(conv_fwd_s1_persist_kernel<16, 8>);
-  if (rows == 8 && c == 32) return go(conv_fwd_s1_persist_kernel<32, 8>);
-  if (rows == 8 && c == 64) return go(conv_fwd_s1_persist_kernel<64, 8>);
-  if (rows == 4 && c == 64) return go(conv_fwd_s1_persist_kernel<64, 4>);
-  return -1;
-}
-
 DTF_API int dtf_dw_slab_reduce(const float* slab, const int4* red, int nmembers, float* grads, long g_mstride,
                                long g_off, int c, hipStream_t stream) {
   if (nmembers <= 0) return 0;
@@ -2656,25 +2522,6 @@ DTF_API int dtf_conv_bwd_fused(const ConvArgs* args, int c, int mode_dy, int epi
   FUSED_CASE(16, 2, 11)  // v1 conv_a + the previous block's BN_b backward sums (x-hat of x3) in the epilogue
   FUSED_CASE(32, 2, 11)
   FUSED_CASE(64, 2, 11)
-  return -1;
-}
-
-DTF_API int dtf_conv_bwd_dual(const ConvArgs* a, const ConvArgs* b, int c, int mode_dy, int epi, int nblocks, int lds,
-                              hipStream_t stream) {
-  if (nblocks <= 0) return 0;
-  DTF_HOST_CHECK(lds <= 160 * 1024);
-  DTF_HOST_CHECK(a->work != nullptr && b->work != nullptr && a->n_main >= 0 && b->n_main >= 0);
-  DTF_HOST_CHECK(nblocks >= a->n_main + b->n_main);
-#define DUAL_CASE(CC, M, E)                                                                                  \
-  if (c == CC && mode_dy == M && epi == E) {                                                                \
-    hipLaunchKernelGGL((conv_bwd_dual_kernel<CC, M, E>), dim3(nblocks), dim3(256), lds, stream, *a, *b);    \
-    return DTF_CHECK_LAUNCH();                                                                              \
-  }
-  DUAL_CASE(16, 0, 0) DUAL_CASE(32, 0, 0) DUAL_CASE(64, 0, 0)
-  DUAL_CASE(16, 3, 0) DUAL_CASE(32, 3, 0) DUAL_CASE(64, 3, 0)
-  DUAL_CASE(16, 2, 0) DUAL_CASE(32, 2, 0) DUAL_CASE(64, 2, 0)
-  DUAL_CASE(16, 2, 1)
-#undef DUAL_CASE
   return -1;
 }
 

@@ -1,6 +1,6 @@
 """A/B of the step plans' work-split constants without editing the engine (diagnostic).
 
-    python tools/ab_bench.py --set FWD_ITERS_PER_WG=1 --set DUAL_WG.64=32 --set DUAL_CS=32:64 -- --pop 8 --steps 60
+    python tools/ab_bench.py --set FWD_ITERS_PER_WG=1 --set DEFER_WG.64=32 --set DEFER_MID_CS=32:64 -- --pop 8 --steps 60
 
 Each ``--set`` overrides one module constant of ``engine/hip_resnet.py`` in this process only: ``NAME=int``,
 ``NAME.key=int`` for a dict constant, ``NAME=a:b:c`` for a tuple of ints, ``NAME=`` empties a dict constant;

@@ -3,6 +3,10 @@
 Forward (statistics epilogue) and data gradient (A operand from the forward weight layout, ReLU mask by BN(xm),
 BN-backward statistics) at every instantiated geometry: 56 x 56 x 64 (8-row tiles of 448 pixels), 28 x 28 x 128
 (8-row tiles) and 14 x 14 x 256 (whole images in 224-pixel tiles); two members with their own weight rows.
+
+The folded forward (``dtf_convg_t3`` mode 1, convg_t3_kernel XF: relu(x * scale + shift) applied while the input rows
+are staged, padding left zero) at the same geometries is compared bitwise with a float64 reference on small-integer
+operands (tests/_convg_exact.py ``t3_fold_case``: |y| <= 256 and sum(y^2) < 2^24 are asserted on the reference first).
 """
 import ctypes
 
@@ -86,3 +90,42 @@ def test_convg_t3_matches_torch(hw, c, dgrad, flags):
             s0, s1 = out.sum((0, 1, 2)), (out * out).sum((0, 1, 2))
         assert _relerr(out, ref) < 1e-2, (s, _relerr(out, ref))
         assert _relerr(sth[s, 0, :c], s0) < 1e-3 and _relerr(sth[s, 1, :c], s1) < 1e-3
+
+
+@pytest.mark.parametrize("hw,c", [(56, 64), (28, 128), (14, 256)])
+@pytest.mark.parametrize("flags", [1, 0])
+def test_convg_t3_folded_forward_is_exact(hw, c, flags):
+    """mode 1 (XF), forward: output and both statistics rows of members in slots 0 and 2 (capacity 3) equal the
+    float64 reference bit for bit; the statistics row of the unused slot stays zero."""
+    import _convg_exact as cx
+    ops, hi, dev, det = cx.gpu_env()
+    k = cx.t3_fold_case(hw, c)
+    dt = ops.act_dtype()
+    cx.check_t3_fold(k, dt)  # the reference alone
+    n = k.x.shape[0]
+    xd, wd, cd = k.x.to(dt).to(dev), k.w.to(dt).to(dev), k.coef.float().to(dev)
+    y = torch.full((n, hw, hw, c), cx.Y_CANARY, dtype=dt, device=dev)
+    st = torch.zeros(cx.CAP, 2, cx.CMAX, dtype=torch.int64 if det else torch.float32, device=dev)
+    rows = hi._CG_T3[hw]
+    tc = 64 if hw == 56 else 128
+    items = [[s, (img * hw + y0) * hw, (img * hw + y0 + rows) * hw, o0] for s, f, e in cx.member_ranges(k.sizes)
+             for img in range(f, e) for y0 in range(0, hw, rows) for o0 in range(0, c, tc)]
+    work = torch.tensor(items, dtype=torch.int32, device=dev)
+    a = hi.CgArgs()
+    a.x, a.y, a.w, a.work, a.st_out, a.c_in = (xd.data_ptr(), y.data_ptr(), wd.data_ptr(), work.data_ptr(),
+                                               st.data_ptr(), cd.data_ptr())
+    a.w_mstride, a.w_off = c * 9 * c, 0
+    a.Hi = a.Wi = a.Ho = a.Wo = hw
+    a.Ci = a.Co = c
+    a.kh = a.kw = 3
+    a.stride, a.pad, a.cmax, a.log2ci, a.flags = 1, 1, cx.CMAX, c.bit_length() - 1, flags
+    rc = ops.lib().dtf_convg_t3(ctypes.byref(a), tc, 4, 0, hw, work.shape[0], 1, ops.stream())
+    assert rc == 0, rc
+    torch.cuda.synchronize()
+    got = y.cpu().double()
+    if not torch.equal(got, k.y):
+        bad = (got != k.y).nonzero()
+        i, r, col, o = (int(v) for v in bad[0])
+        pytest.fail("%d outputs differ; first: image %d row %d column %d channel %d: got %r want %r" % (
+            bad.shape[0], i, r, col, o, float(got[i, r, col, o]), float(k.y[i, r, col, o])))
+    assert torch.equal(cx.acc_download(st, cx.FX_STAT, det), k.st.float())

@@ -7,7 +7,7 @@
 //                     and dgamma / dbeta into the gradient row
 //   cg_bn_bwd_apply : g = A dz + B h + C (+ add)   (the residual-stream gradient through the first BN of a block)
 //   cg_prep_input   : fp32 NHWC images -> bf16 with channels zero-padded to 8
-//   cg_maxpool_fwd / cg_maxpool_bwd : 3x3/2 'SAME' (TF pads the end) max-pool with a per-output argmax byte;
+//   cg_maxpool_fwd / cg_maxpool_bwd : 3x3/2 end-padded max-pool (TF 'SAME' at even sizes) with a per-output argmax byte;
 //                     the backward gathers (no atomics): every input pixel sums the <= 4 windows choosing it
 //   cg_gap          : final BN+ReLU + global average pool -> bf16 features (dense GEMM operand)
 //   cg_softmax_ce   : + bias, softmax cross-entropy, loss / correct count, dlogits (bf16, padded), dbias
@@ -400,7 +400,10 @@ __global__ __launch_bounds__(256) void cg_prep_input_s2d_kernel(const float* __r
   }
 }
 
-// 3x3 stride-2 max-pool, output o covers input rows / cols 2o .. 2o+2 (TF 'SAME': the pad is at the end)
+// 3x3 stride-2 max-pool, output o covers input rows / cols 2o .. 2o+2 clipped to the image, Ho = ceil(H / 2): the pad
+// is always at the END.  At even sizes (every shape of the engine: image_size % 32 == 0) that is TF 'SAME'; at odd
+// sizes it is NOT (TF 'SAME' and models/resnet.py pad one row / column BEFORE there).  The first tap in row-major
+// order that attains the maximum wins a tie (strict >); am holds its absolute tap number 3 dy + dx.
 __global__ __launch_bounds__(256) void cg_maxpool_fwd_kernel(const bf16_t* __restrict__ x, bf16_t* __restrict__ y,
                                                               uint8_t* __restrict__ am, int H, int W, int Ho, int Wo,
                                                               int C, long total8) {
@@ -1109,6 +1112,8 @@ DTF_API int dtf_cg_prep_input_s2d(const float* x, bf16_t* y, int N, int H, int W
   return DTF_CHECK_LAUNCH();
 }
 
+// Ho = ceil(H / 2), Wo = ceil(W / 2).  Odd H / W are end-padded (clipped last window), which is not TF 'SAME' there;
+// tests/test_gpu_convg_aux.py holds both backward kernels to that contract.
 DTF_API int dtf_cg_maxpool(const bf16_t* x, bf16_t* y, uint8_t* am, const bf16_t* g, bf16_t* dx, int N, int H, int W,
                            int Ho, int Wo, int C, int backward, hipStream_t stream) {
   if (C % 8) return -2;

@@ -71,6 +71,9 @@ __device__ void run_row(float* __restrict__ w, float* __restrict__ a, float* __r
     float bb[4] = {bv.x, bv.y, bv.z, bv.w};
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
+      // the last float4 of a row with P % 4 != 0 reaches into the padding, whose weights, slots and gradients are
+      // zero: Adagrad's 0 * rsqrtf(0) there is NaN, so those lanes keep their words
+      if (i + j >= P) continue;
       float g = gg[j] * gscale;  // static loss scaling (fp16): the gradients of S * loss, unscaled here
       if (h.reg != 0 && i + j < n_reg) g = reg_grad(g, ww[j], h.wd, h.reg);
       update1<OPT>(ww[j], aa[j], bb[j], g, h, lr_t);

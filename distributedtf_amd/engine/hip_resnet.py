@@ -36,7 +36,8 @@ from .. import ops
 from ..data.datasets import IndexBatch, batch_len
 from ..models.resnet import BN_EPS
 from .hip_step import (HipBackend, LossRing, PinnedStager, _LIVE_GRAPH_PLANS, _p, advance_steps,  # noqa: F401
-                       graph_state, note_step_advanced, release_graphs, run_captured, same_batches, upload_hyper)
+                       graph_state, note_step_advanced, release_graphs, run_captured, run_optimizer, same_batches,
+                       upload_hyper)
 
 def _nrep() -> int:
     """BN statistic replicas, as compiled into the loaded library (common.h DTF_NREP; 64 in the deterministic
@@ -198,6 +199,7 @@ class HeadArgs(ctypes.Structure):
         ("g_mstride", c_long), ("st_f", c_void_p), ("st_b", c_void_p), ("cnt", c_void_p), ("dfeat", c_void_p),
         ("loss", c_void_p), ("correct", c_void_p), ("logits_out", c_void_p), ("hw", c_int), ("C", c_int),
         ("ncls", c_int), ("train", c_int), ("slab", c_void_p), ("slab_b", c_void_p), ("loss_scale", ctypes.c_float),
+        ("scale_tab", c_void_p),
     ]
 
 
@@ -358,6 +360,7 @@ class HipResNetBackend(HipBackend):
     accepts_index_batches = True
     _plan_cls = None  # _StepPlan (set below)
     max_eval_plans = 9
+    dynamic_loss_scale_ok = True
 
     def __init__(self, engine):
         _register()
@@ -375,6 +378,8 @@ class HipResNetBackend(HipBackend):
             "the loaded kernel library (%s) does not match compute dtype %s: fp16 needs DTF_HALF=1" % (
                 "fp16" if self.half else "bf16", engine.compute_dtype)
         self.loss_scale = float(engine.loss_scale) if self.half else 1.0
+        if engine.dynamic_loss_scale and not self.half:
+            raise ValueError("dynamic loss scaling is for the fp16 build of the HIP step (bf16 needs no loss scaling)")
         NREP = self.nrep = _nrep()
         self.stats_bn_stride = cap * NREP * 128
         # [fwd | bwd] statistic accumulators: zeroed by ONE memset per step
@@ -1313,6 +1318,7 @@ class _StepPlan:
         ha.logits_out = None
         ha.hw, ha.C, ha.ncls, ha.train = hw, cfg.final_size, cfg.num_classes, 1
         ha.loss_scale = be.loss_scale
+        ha.scale_tab = _p(e.lscale) if e.dynamic_loss_scale else None  # per-member dynamic scale
         self._head_slab(ha, hwork)
         self._keep(ha)
         self._add(lib.dtf_head, ctypes.byref(ha), hwork.shape[0])
@@ -1575,6 +1581,7 @@ class _StepPlan:
         ha_.logits_out = None
         ha_.hw, ha_.C, ha_.ncls, ha_.train = hw, cfg.final_size, cfg.num_classes, 1
         ha_.loss_scale = be.loss_scale
+        ha_.scale_tab = _p(e.lscale) if e.dynamic_loss_scale else None
         self._head_slab(ha_, hwork)
         self._keep(ha_)
         self._add(lib.dtf_head, ctypes.byref(ha_), hwork.shape[0])
@@ -1669,9 +1676,7 @@ class _StepPlan:
                 ops.augment_cifar(self.src.train_x, self.src.train_y, self.idx, self.rng, True, out16=self.xin16,
                                   lab32=self.labels, member_keys=(self.img_slot, e.state, e.S, 3 * e.Pp + e.R))
             elif fn == "optim":
-                e.dp_sync_grads(self.slots)  # data-parallel member groups only (no-op otherwise)
-                ops.fused_optimizer(e.state, e.grads, e.hyper, e.Pp, e.P, e.n_reg, shadow=None, zero_grads=True,
-                                    grad_scale=1.0 / self.be.loss_scale)
+                run_optimizer(e, self.be, self.slots, self.slots_t, None)  # (+ dynamic loss scaling: hip_step.py)
             elif fn == "step":
                 # step counters + per-member losses gathered inside the step (graph) so a replay leaves one copy
                 # for loss_view

@@ -101,6 +101,27 @@ def advance_steps(e, slots_long, slots_i32=None, loss=None, loss_sel=None, ring=
         torch.index_select(loss, 0, slots_long, out=loss_sel)
 
 
+def run_optimizer(e, be, slots, slots_i32, shadow):
+    """The "optim" marker of a step's launch list (inside the captured graph): the gradient all-reduce of
+    data-parallel member groups, then the fused optimizer, which unscales by the backend's static ``loss_scale``.
+
+    With dynamic loss scaling (``e.dynamic_loss_scale``) the sequence is: all-reduce; the finiteness pass over the
+    listed members' gradient rows (after the all-reduce, so every replica of a member decides alike); the fused
+    optimizer reading the table (a flagged member keeps weights, slots and shadow, its gradients are zeroed); the
+    scale rule.  No host synchronisation: the table lives on the device and the host reads it only on logging steps
+    and at round end.  A skipped step still consumes its batch, still advances the step counters (the "step" marker
+    that follows: the host mirrors ``host_step`` / ``_hyper_dev`` and PBT's lockstep rounds stay valid) and still
+    updates the BN moving statistics (forward-only, independent of the scale)."""
+    e.dp_sync_grads(slots)  # data-parallel member groups only (no-op otherwise)
+    if not e.dynamic_loss_scale:
+        ops.fused_optimizer(e.state, e.grads, e.hyper, e.Pp, e.P, e.n_reg, shadow=shadow, zero_grads=True,
+                            grad_scale=1.0 / be.loss_scale)
+        return
+    ops.grad_finite_check(e.grads, e.Pp, e.P, slots_i32, e.lscale)
+    ops.fused_optimizer(e.state, e.grads, e.hyper, e.Pp, e.P, e.n_reg, shadow=shadow, zero_grads=True, lscale=e.lscale)
+    ops.loss_scale_update(e.lscale, e.hyper, slots_i32, e.loss_scale_growth_steps)
+
+
 class LossRing:
     """Per-step member losses without a per-step copy: the captured step's step_end kernel writes each replay's
     losses into the next row of a [rows, n] device ring (the row index lives on the device), and the host hands out
@@ -221,8 +242,12 @@ class HipBackend:
     eval_chunk_env, eval_chunk = "DTF_EVAL_CHUNK", 2000  # images per eval forward: env switch, default
     shadow = None  # low-precision copy of the master rows that the fused optimizer also writes (bf16 families)
     loss_scale = 1.0  # static loss scaling of the fp16 builds
+    dynamic_loss_scale_ok = False  # the family's head reads the engine's dynamic loss-scale table (CIFAR ResNet)
 
     def __init__(self, engine):
+        if getattr(engine, "dynamic_loss_scale", False) and not self.dynamic_loss_scale_ok:
+            raise ValueError("dynamic loss scaling: %s has no dynamic path (the fp16 CIFAR ResNet HIP step and the "
+                             "torch backend have)" % type(self).__name__)
         self.e = engine
         self.dev = engine.device
         self._plans = {}
@@ -313,9 +338,7 @@ class HipPlan:
             if fn == "zero":
                 args[0].zero_()
             elif fn == "optim":
-                e.dp_sync_grads(self.slots)  # data-parallel member groups only (no-op otherwise)
-                ops.fused_optimizer(e.state, e.grads, e.hyper, e.Pp, e.P, e.n_reg, shadow=be.shadow,
-                                    zero_grads=True, grad_scale=1.0 / be.loss_scale)
+                run_optimizer(e, be, self.slots, self.slots_t, be.shadow)
             elif fn == "step":
                 # step counters + per-member losses gathered inside the step (graph): a replay leaves one copy
                 advance_steps(e, self.slots_long, self.slots_t, be.loss, self.loss_sel)

@@ -44,6 +44,35 @@ RMSPROP_EPS = 1e-10
 ADAGRAD_INIT = 0.1
 
 
+# dynamic loss scaling (fp16): columns of a member's row of the engine's ``lscale`` table and the rule's constants
+# (TF's DynamicLossScale defaults: initial scale 2^15, growth after 2000 clean steps, factor 2)
+LS_SCALE, LS_GOOD, LS_FOUND_INF, LS_SKIPPED = range(4)
+LOSS_SCALE_INIT = 2.0 ** 15
+LOSS_SCALE_MAX = 2.0 ** 24
+LOSS_SCALE_GROWTH_STEPS = 2000
+
+
+def loss_scale_update(row, growth_interval: int = LOSS_SCALE_GROWTH_STEPS):
+    """The dynamic loss-scale rule on one table row ``[scale, good_steps, found_inf, skipped_total]`` -> new row.
+
+    Overflow (``found_inf != 0``; the optimizer skipped the update): the scale halves (floor 1), the run of clean
+    steps restarts, ``skipped_total`` counts the step.  Clean step: ``good_steps += 1`` and, once ``growth_interval``
+    clean steps ran in a row, the scale doubles (cap 2^24) and the run restarts.  ``found_inf`` is cleared.  Every
+    value is a power of two or a small integer, so fp32 on the device (optim.hip ``loss_scale_update_kernel``)
+    and Python floats here agree exactly."""
+    scale, good, found, skipped = (float(v) for v in row)
+    if found != 0.0:
+        scale = max(scale * 0.5, 1.0)
+        good = 0.0
+        skipped += 1.0
+    else:
+        good += 1.0
+        if good >= float(growth_interval):
+            scale = min(scale * 2.0, LOSS_SCALE_MAX)
+            good = 0.0
+    return [scale, good, 0.0, skipped]
+
+
 def slot_init_values(optimizer: str):
     """Initial values of (slot1, slot2) for a freshly created member."""
     if optimizer == "Adagrad":

@@ -42,7 +42,9 @@ def _align(n: int, a: int = 64) -> int:
 
 class PopulationEngine:
     def __init__(self, arch, capacity: int, device, backend: str = "auto", compute_dtype=torch.bfloat16,
-                 optimizer_impl: str = "auto", loss_scale: float = 1.0):
+                 optimizer_impl: str = "auto", loss_scale=1.0,
+                 loss_scale_growth_steps: int = _optim.LOSS_SCALE_GROWTH_STEPS,
+                 initial_loss_scale: float = _optim.LOSS_SCALE_INIT):
         self.arch = arch
         self.capacity = int(capacity)
         self.device = torch.device(device)
@@ -60,7 +62,17 @@ class PopulationEngine:
         self.compute_dtype = compute_dtype
         if self.device.type == "cpu" and compute_dtype == torch.bfloat16:
             self.compute_dtype = torch.float32
-        self.loss_scale = float(loss_scale)  # static loss scaling of the PyTorch path (fp16; resnet_run_loop.py:284)
+        # loss scaling (fp16; resnet_run_loop.py:284): a static factor, or "dynamic" -- per member, on the device:
+        # lscale[slot] = [scale, good_steps, found_inf, skipped_total] (optim.loss_scale_update).  The table is not
+        # part of the state row: the exploit payload and the checkpoint tensors keep their layout
+        self.dynamic_loss_scale = loss_scale == "dynamic"
+        self.initial_loss_scale = float(initial_loss_scale)
+        self.loss_scale_growth_steps = int(loss_scale_growth_steps)
+        if self.loss_scale_growth_steps < 1:
+            raise ValueError("loss_scale_growth_steps must be >= 1")
+        self.loss_scale = self.initial_loss_scale if self.dynamic_loss_scale else float(loss_scale)
+        self.lscale = torch.zeros(self.capacity, 4, dtype=torch.float32, device=self.device)
+        self.lscale[:, _optim.LS_SCALE] = self.initial_loss_scale
         self.dp = None  # parallel.dataparallel.DPContext when a member is trained by a group of ranks
         # data parallelism: this replica's gradient weight per member row (local shard / member batch), a device
         # buffer so the captured step graph reads the current step's weights
@@ -110,6 +122,7 @@ class PopulationEngine:
         if s2:
             row[2 * self.Pp:2 * self.Pp + self.P] = s2
         self.host_step[slot] = 0
+        self.set_loss_scale_row(slot, [self.initial_loss_scale, 0.0, 0.0, 0.0])
         self.backend.on_params_changed([slot])
         return slot
 
@@ -124,7 +137,19 @@ class PopulationEngine:
         counter -- always known on the host (all-gathered with the scores, or sent on the control plane), so an
         import never reads the device row back (no sync that would drain the queued steps)."""
         self.host_step[slot] = int(step)
+        if self.dynamic_loss_scale:
+            # the imported weights start from the initial scale (the loser's own scale described other weights; the
+            # winner's never travels: the same rule wherever the winner lives); the skip count stays the member's.
+            # Device-side column writes: no readback
+            self.lscale[slot, :_optim.LS_SKIPPED] = torch.tensor([self.initial_loss_scale, 0.0, 0.0])
         self.backend.on_params_changed([slot])
+
+    def loss_scale_row(self, slot: int):
+        """[scale, good_steps, found_inf, skipped_total] of a member (a host read: logging steps / round end only)."""
+        return [float(v) for v in self.lscale[slot].cpu().tolist()]
+
+    def set_loss_scale_row(self, slot: int, row) -> None:
+        self.lscale[slot] = torch.tensor([float(v) for v in row], dtype=torch.float32)
 
     # --------------------------------------------------------------- training
     def set_hyper(self, slot: int, hparams: Dict, lr: float, active: bool = True) -> None:
@@ -153,6 +178,8 @@ class PopulationEngine:
         self._hyper_dev = None
         losses = self.backend.forward_backward(slots, batches)
         self.dp_sync_grads(slots)
+        if self.dynamic_loss_scale:
+            self._dynamic_unscale(slots)
         self.apply_optimizer(slots)
         for s in slots:
             self.host_step[s] += 1
@@ -200,6 +227,24 @@ class PopulationEngine:
         r = self.state[:, lo:hi].index_select(0, idx)
         self.dp.allreduce_mean_(r)
         self.state[:, lo:hi].index_copy_(0, idx, r)
+
+    def _dynamic_unscale(self, slots: Sequence[int]) -> None:
+        """Dynamic loss scaling on the PyTorch path (the HIP step does the same on the device, hip_step.run_optimizer):
+        the gradient rows hold the gradients of scale * loss; after the data-parallel all-reduce, so every replica
+        decides alike.  A member with Inf / NaN in its row skips this update -- its optimizer row goes inactive and its
+        gradients are zeroed; the others are unscaled.  Then the scale rule.  A skipped step still consumes its batch,
+        advances the step counters and has already updated the BN moving statistics (forward-only)."""
+        rows = self.lscale.cpu().tolist()
+        for s in slots:
+            g = self.grads[s, :self.P]
+            found = not bool(torch.isfinite(g).all())
+            if found:
+                self.hyper[s, _optim.H_ACTIVE] = 0.0
+                self.grads[s].zero_()
+            else:
+                g.div_(rows[s][_optim.LS_SCALE])
+            rows[s][_optim.LS_FOUND_INF] = 1.0 if found else 0.0
+            self.set_loss_scale_row(s, _optim.loss_scale_update(rows[s], self.loss_scale_growth_steps))
 
     def apply_optimizer(self, slots: Sequence[int]) -> None:
         if self.optimizer_impl == "hip":
@@ -269,7 +314,10 @@ class TorchBackend:
             if self.keep_probs:
                 self._probs[s] = torch.softmax(logits.detach().float(), dim=1)
             loss = F.cross_entropy(logits.float(), y.long())
-            if e.loss_scale != 1.0:
+            if e.dynamic_loss_scale:
+                # the member's own scale; unscaled after the finiteness check (PopulationEngine._dynamic_unscale)
+                g, = torch.autograd.grad(loss * float(e.lscale[s, _optim.LS_SCALE]), p)
+            elif e.loss_scale != 1.0:
                 g, = torch.autograd.grad(loss * e.loss_scale, p)
                 g = g / e.loss_scale
             else:

@@ -98,11 +98,14 @@ class EngineModel(ModelBase):
     def __init__(self, cluster_id, hparams, save_base_dir, seed=None, device=None, backend="auto",
                  capacity=8, use_synthetic_data=None, data_dir=None, max_train_steps=None,
                  checkpoint_every_round=True, eval_every_round=True, dp=None, tf_checkpoint=False, ready_steps=None,
-                 stop_threshold=None, batch_size=None, dtype="bf16", loss_scale=1.0, epochs_between_evals=1, **kw):
+                 stop_threshold=None, batch_size=None, dtype="bf16", loss_scale=1.0, epochs_between_evals=1,
+                 loss_scale_growth_steps=None, **kw):
         super().__init__(cluster_id, hparams, save_base_dir, seed=seed)
         from ..utils.flags import get_dtype
         self.compute_dtype = get_dtype(dtype)  # --dtype: bf16 (HIP kernels) | fp32 / fp16 (PyTorch backend)
-        self.loss_scale = float(loss_scale or 1.0)
+        # --loss_scale: a static factor, or "dynamic" (per-member dynamic loss scaling; PopulationEngine.lscale)
+        self.loss_scale = "dynamic" if loss_scale == "dynamic" else float(loss_scale or 1.0)
+        self.loss_scale_growth_steps = int(loss_scale_growth_steps) if loss_scale_growth_steps else None
         self.ready_steps = int(ready_steps) if ready_steps else None  # PBT ready interval in steps (--ready_steps)
         self.stop_threshold = stop_threshold  # --stop_threshold: end a member's train call once eval passes it
         # --epochs_between_evals: epochs per train -> eval cycle (reference _base.py:74-79, resnet_run_loop.py:446-447)
@@ -119,7 +122,8 @@ class EngineModel(ModelBase):
         self.tf_checkpoint = tf_checkpoint  # also export the reference's TF tensor-bundle format every round
         self.eval_every_round = eval_every_round
         self.arch = self.make_arch()
-        key = (type(self).__name__, str(self.device), self.arch.name, backend, self.compute_dtype, self.loss_scale)
+        key = (type(self).__name__, str(self.device), self.arch.name, backend, self.compute_dtype, self.loss_scale,
+               self.loss_scale_growth_steps)
         eng = EngineModel._engines.get(key)
         if eng is None or not eng.free_slots:
             eng = self._grow_or_create(key, eng, capacity, backend)
@@ -134,11 +138,14 @@ class EngineModel(ModelBase):
 
     def _grow_or_create(self, key, eng, capacity, backend):
         kw = dict(backend=backend, compute_dtype=self.compute_dtype, loss_scale=self.loss_scale)
+        if self.loss_scale_growth_steps:
+            kw["loss_scale_growth_steps"] = self.loss_scale_growth_steps
         if eng is None:
             eng = PopulationEngine(self.arch, capacity, self.device, **kw)
         else:
             new = PopulationEngine(self.arch, eng.capacity * 2, self.device, **kw)
             new.state[:eng.capacity].copy_(eng.state)
+            new.lscale[:eng.capacity].copy_(eng.lscale)
             new.members = dict(eng.members)
             new.free_slots = [s for s in range(new.capacity) if s not in new.members]
             new.host_step[:eng.capacity] = eng.host_step
@@ -277,10 +284,16 @@ class EngineModel(ModelBase):
         if g is not None and getattr(self, "_perm_gen_state", None) is not None:
             d["data"] = {"perm_gen": self._perm_gen_state.cpu().numpy().tobytes().hex(), "perm_pos": self._perm_pos,
                          "gen": g.get_state().cpu().numpy().tobytes().hex()}
+        if self.engine.dynamic_loss_scale:
+            # the member's dynamic loss-scale row (not part of the state row): a resumed run continues with its scale
+            d["loss_scale"] = self.engine.loss_scale_row(self.slot)
         return d
 
     def restore_stream_state(self, d) -> None:
         super().restore_stream_state(d)
+        row = (d or {}).get("loss_scale")
+        if row is not None and self.engine.dynamic_loss_scale:
+            self.engine.set_loss_scale_row(self.slot, row)  # (after the checkpoint import, which reset the row)
         data = (d or {}).get("data")
         if data is None:
             return
@@ -488,9 +501,20 @@ class EngineModel(ModelBase):
             pr = fn([m.slot for m in active]) if fn is not None else None
             return None if pr is None else [None if t is None else t.cpu().numpy() for t in pr]
 
+        def loss_scale_col(col):
+            def fetch():  # one readback of the table, on logging steps only
+                if "ls" not in host:
+                    host["ls"] = eng.lscale.cpu().tolist()
+                return [host["ls"][m.slot][col] for m in active]
+            return fetch
+
+        extra = {"probabilities": probabilities}
+        if eng.dynamic_loss_scale:
+            from ..engine.optim import LS_SCALE, LS_SKIPPED
+            extra.update(loss_scale=loss_scale_col(LS_SCALE), skipped_steps=loss_scale_col(LS_SKIPPED))
         values = _LazyValues(device_values, {"images": n_img, "model_ids": [m.cluster_id for m in active],
                                              "learning_rate": list(lrs), "sync": eng.device.type == "cuda"},
-                             extra={"probabilities": probabilities})
+                             extra=extra)
         for h in due:
             h.after_step(step, values)
 

@@ -26,6 +26,10 @@ c_void_p, c_int, c_long, c_float = ctypes.c_void_p, ctypes.c_int, ctypes.c_long,
 _SIGNATURES = {
     "dtf_fused_optimizer": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_long, c_long, c_long, c_long, c_int,
                             c_float, c_void_p],
+    "dtf_fused_optimizer_dyn": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_long, c_long, c_long, c_long, c_int,
+                                c_float, c_void_p, c_void_p],
+    "dtf_grad_finite_check": [c_void_p, c_long, c_long, c_void_p, c_int, c_void_p, c_void_p],
+    "dtf_loss_scale_update": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p],
     "dtf_shadow_refresh": [c_void_p, c_void_p, c_void_p, c_int, c_long, c_long, c_long, c_void_p],
     "dtf_step_advance": [c_void_p, c_long, c_long, c_void_p, c_int, c_void_p, c_int, c_void_p],
     "dtf_step_end": [c_void_p, c_long, c_long, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
@@ -212,16 +216,41 @@ def check(err, name):
         raise RuntimeError("%s launch failed: hipError %d" % (name, err))
 
 
-def fused_optimizer(state, grads, hyper, Pp, P, n_reg, shadow=None, zero_grads=True, grad_scale=1.0):
+def fused_optimizer(state, grads, hyper, Pp, P, n_reg, shadow=None, zero_grads=True, grad_scale=1.0, lscale=None):
     """One launch: TF1-semantics optimizer step for every member row (see optim.hip).  ``grad_scale`` multiplies every
-    gradient first (1 / loss_scale: the fp16 mode's static loss scaling, resnet_run_loop.py:284-294)."""
+    gradient first (1 / loss_scale: the fp16 mode's static loss scaling, resnet_run_loop.py:284-294).  ``lscale``:
+    the dynamic loss-scale table [G, 4] instead -- each member unscales by its own scale and a member whose
+    ``found_inf`` is set skips its update (``dtf_fused_optimizer_dyn``)."""
     assert state.is_cuda and state.dtype == torch.float32 and state.is_contiguous()
     assert grads.shape[1] == Pp and hyper.shape[1] == 8
     G = state.shape[0]
     if shadow is not None:
         assert shadow.dtype in (torch.bfloat16, torch.float16) and shadow.shape[1] == Pp
+    if lscale is not None:
+        assert lscale.dtype == torch.float32 and tuple(lscale.shape) == (G, 4) and lscale.is_contiguous()
+        check(lib().dtf_fused_optimizer_dyn(ptr(state), ptr(grads), ptr(hyper), ptr(shadow), G, state.shape[1], Pp, P,
+                                            n_reg, 1 if zero_grads else 0, float(grad_scale), ptr(lscale), stream()),
+              "fused_optimizer_dyn")
+        return
     check(lib().dtf_fused_optimizer(ptr(state), ptr(grads), ptr(hyper), ptr(shadow), G, state.shape[1], Pp, P, n_reg,
                                     1 if zero_grads else 0, float(grad_scale), stream()), "fused_optimizer")
+
+
+def grad_finite_check(grads, Pp, P, slots_t, lscale):
+    """found_inf of every member listed in ``slots_t`` (int32, device) |= its gradient row [0, P) holds Inf / NaN."""
+    assert grads.is_cuda and grads.dtype == torch.float32 and grads.shape[1] == Pp and grads.is_contiguous()
+    assert slots_t.dtype == torch.int32 and lscale.dtype == torch.float32 and lscale.shape[1] == 4
+    assert 0 < P <= Pp and Pp % 4 == 0 and lscale.shape[0] == grads.shape[0]
+    check(lib().dtf_grad_finite_check(ptr(grads), Pp, P, ptr(slots_t), slots_t.numel(), ptr(lscale), stream()),
+          "grad_finite_check")
+
+
+def loss_scale_update(lscale, hyper, slots_t, growth_interval):
+    """The dynamic loss-scale rule (engine/optim.py ``loss_scale_update``) for every active listed member."""
+    assert lscale.dtype == torch.float32 and lscale.shape[1] == 4 and hyper.shape == (lscale.shape[0], 8)
+    assert slots_t.dtype == torch.int32 and int(growth_interval) >= 1
+    check(lib().dtf_loss_scale_update(ptr(lscale), ptr(hyper), ptr(slots_t), slots_t.numel(), int(growth_interval),
+                                      stream()), "loss_scale_update")
 
 
 def shadow_refresh(state, shadow, rows, Pp, P):

@@ -94,10 +94,26 @@ __device__ void run_row(float* __restrict__ w, float* __restrict__ a, float* __r
 __global__ __launch_bounds__(256) void fused_optimizer_kernel(float* __restrict__ state, float* __restrict__ grads,
                                                                const float* __restrict__ hyper, bf16_t* __restrict__ shadow,
                                                                long S, long Pp, long P, long n_reg, int zero_grads,
-                                                               float gscale) {
+                                                               float gscale, const float* __restrict__ lscale) {
   const int g = blockIdx.y;
   const float* hp = hyper + g * 8;
   if (hp[7] == 0.f) return;
+  if (lscale != nullptr) {
+    // dynamic loss scaling: the member's own scale (a power of two, so the reciprocal is exact) and, when the
+    // finiteness pass flagged its gradients, the skip path -- weights, slots and shadow keep every bit, the
+    // gradient row is zeroed as below so no Inf / NaN reaches the next step.  Block-uniform: one row per blockIdx.y
+    const float* ls = lscale + g * 4;
+    gscale = 1.f / ls[0];
+    if (ls[2] != 0.f) {
+      if (zero_grads) {
+        float* gr = grads + (long)g * Pp;
+        const long stride = (long)gridDim.x * blockDim.x * 4;
+        for (long i = ((long)blockIdx.x * blockDim.x + threadIdx.x) * 4; i < P; i += stride)
+          *reinterpret_cast<float4*>(gr + i) = make_float4(0.f, 0.f, 0.f, 0.f);
+      }
+      return;
+    }
+  }
   Hyper h;
   h.opt = (int)hp[0];
   h.lr = hp[1];
@@ -164,7 +180,78 @@ __global__ void step_advance_kernel(float* __restrict__ state, long S, long col,
   }
 }
 
+// Dynamic loss scaling (fp16).  Per-member table row (4 floats): [scale, good_steps, found_inf, skipped_total]; every
+// value is a power of two or a small integer, so the arithmetic below is exact.
+//
+// Finiteness pass over the gradient rows of the listed members: found_inf |= any Inf / NaN in grads[slot][0, P).
+// Streaming (the one extra read of the gradients per step; the optimizer that follows finds them in cache):
+// 16 B per lane, grid-stride, blockIdx.y = listed member.  The test is on the exponent bits, not a float compare.
+// Lanes of the last float4 past P are ignored (the load stays inside the row: Pp is a multiple of 4).  A wave that
+// found something stores the constant 1.0f from one lane: concurrent stores of the same value need no atomic.
+__global__ __launch_bounds__(256) void grad_finite_check_kernel(const float* __restrict__ grads, long Pp, long P,
+                                                                 const int* __restrict__ slots,
+                                                                 float* __restrict__ lscale) {
+  const int s = slots[blockIdx.y];
+  const float* gr = grads + (long)s * Pp;
+  const long stride = (long)gridDim.x * blockDim.x * 4;
+  int bad = 0;
+  for (long i = ((long)blockIdx.x * blockDim.x + threadIdx.x) * 4; i < P; i += stride) {
+    const uint4 v = *reinterpret_cast<const uint4*>(gr + i);
+    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if (i + j < P && (w[j] & 0x7f800000u) == 0x7f800000u) bad = 1;
+  }
+  if (__any(bad) && (threadIdx.x & 63) == 0) lscale[s * 4 + 2] = 1.0f;
+}
+
+// The scale rule, one thread per listed member (active ones only: hyper column 7), after the optimizer read the row:
+// overflow -> scale = max(scale / 2, 1), good = 0, skipped += 1; clean -> good += 1 and, at growth_interval clean
+// steps in a row, scale = min(2 * scale, 2^24), good = 0.  found_inf is cleared for the next step.
+// (engine/optim.py loss_scale_update is the same rule on the host.)
+__global__ void loss_scale_update_kernel(float* __restrict__ lscale, const float* __restrict__ hyper,
+                                         const int* __restrict__ slots, int n, int growth_interval) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int s = slots[i];
+  if (hyper[s * 8 + 7] == 0.f) return;
+  float* r = lscale + s * 4;
+  float scale = r[0], good = r[1];
+  if (r[2] != 0.f) {
+    scale = fmaxf(scale * 0.5f, 1.f);
+    good = 0.f;
+    r[3] += 1.f;
+  } else {
+    good += 1.f;
+    if (good >= (float)growth_interval) {
+      scale = fminf(scale * 2.f, 16777216.f);
+      good = 0.f;
+    }
+  }
+  r[0] = scale;
+  r[1] = good;
+  r[2] = 0.f;
+}
+
 }  // namespace
+
+DTF_API int dtf_grad_finite_check(const float* grads, long Pp, long P, const int* slots, int n, float* lscale,
+                                  hipStream_t stream) {
+  if (n <= 0 || P <= 0) return 0;
+  long blocks = (P + 1023) / 1024;
+  if (blocks > 512) blocks = 512;  // the optimizer's cap
+  hipLaunchKernelGGL(grad_finite_check_kernel, dim3((unsigned)blocks, (unsigned)n), dim3(256), 0, stream, grads, Pp, P,
+                     slots, lscale);
+  return DTF_CHECK_LAUNCH();
+}
+
+DTF_API int dtf_loss_scale_update(float* lscale, const float* hyper, const int* slots, int n, int growth_interval,
+                                  hipStream_t stream) {
+  if (n <= 0) return 0;
+  hipLaunchKernelGGL(loss_scale_update_kernel, dim3((n + 63) / 64), dim3(64), 0, stream, lscale, hyper, slots, n,
+                     growth_interval);
+  return DTF_CHECK_LAUNCH();
+}
 
 DTF_API int dtf_step_advance(float* state, long S, long col, float* hyper, int h_step, const int* slots, int n,
                              hipStream_t stream) {
@@ -186,16 +273,24 @@ DTF_API int dtf_step_end(float* state, long S, long col, float* hyper, int h_ste
 }
 
 // gscale: factor on every gradient before the update (1 / the static loss scale of the fp16 mode, else 1)
-DTF_API int dtf_fused_optimizer(float* state, float* grads, const float* hyper, bf16_t* shadow, int G, long S, long Pp,
-                                long P, long n_reg, int zero_grads, float gscale, hipStream_t stream) {
+// lscale: the dynamic loss-scale table [G][4] (member g unscales by 1 / lscale[g][0] and skips its update when
+// lscale[g][2] != 0), or nullptr for the static gscale
+DTF_API int dtf_fused_optimizer_dyn(float* state, float* grads, const float* hyper, bf16_t* shadow, int G, long S,
+                                    long Pp, long P, long n_reg, int zero_grads, float gscale, const float* lscale,
+                                    hipStream_t stream) {
   if (G <= 0) return 0;
   long per_block = 256 * 4;
   long blocks = (P + per_block - 1) / per_block;
   if (blocks > 512) blocks = 512;  // grid-stride; G*512 blocks >> 256 CUs
   dim3 grid((unsigned)blocks, (unsigned)G);
   hipLaunchKernelGGL(fused_optimizer_kernel, grid, dim3(256), 0, stream, state, grads, hyper, shadow, S, Pp, P, n_reg,
-                     zero_grads, gscale);
+                     zero_grads, gscale, lscale);
   return DTF_CHECK_LAUNCH();
+}
+
+DTF_API int dtf_fused_optimizer(float* state, float* grads, const float* hyper, bf16_t* shadow, int G, long S, long Pp,
+                                long P, long n_reg, int zero_grads, float gscale, hipStream_t stream) {
+  return dtf_fused_optimizer_dyn(state, grads, hyper, shadow, G, S, Pp, P, n_reg, zero_grads, gscale, nullptr, stream);
 }
 
 DTF_API int dtf_shadow_refresh(const float* state, bf16_t* shadow, const int* rows, int nrows, long S, long Pp, long P,

@@ -405,6 +405,20 @@ class SPMDPopulation(_ReportMixin):
                 return graph_state(eng.backend)
         return None
 
+    def _loss_scales(self):
+        """[member id, loss scale, skipped steps] of this rank's members that train with dynamic loss scaling
+        (--loss_scale dynamic): one readback of each engine's table, at round end."""
+        out, tables = [], {}
+        for g in self.worker.worker_graphs if self.is_group_leader else []:
+            eng = getattr(g, "engine", None)
+            if eng is None or not getattr(eng, "dynamic_loss_scale", False):
+                continue
+            if id(eng) not in tables:
+                tables[id(eng)] = eng.lscale.cpu().tolist()
+            row = tables[id(eng)][g.slot]
+            out.append([int(g.cluster_id), float(row[0]), int(row[3])])
+        return out
+
     def log_round_metrics(self, rnd, round_s):
         """Append one JSON line per round to ``savedata/metrics.jsonl``: throughput (images/s of
         the whole job), per-phase times (train / exploit / explore, max over ranks), exploit data-plane bytes and
@@ -417,7 +431,7 @@ class SPMDPopulation(_ReportMixin):
         phases = PHASES.since(getattr(self, "_prev_phases", {}))
         self._prev_phases = PHASES.snapshot()
         parts = self.comm.allgather([delta, [float(v[1]) for v in self._values()], phases, self._graph_state(),
-                                     getattr(self, "_round_bs", [])])
+                                     getattr(self, "_round_bs", []), self._loss_scales()])
         if self.rank != 0:
             return
         d = [p[0] for p in parts]
@@ -440,6 +454,10 @@ class SPMDPopulation(_ReportMixin):
                "step_graph": sorted({str(p[3]) for p in parts}),
                # member id -> batch size trained this round (bench.py --ragged --batch_sizes reproduces the mix)
                "batch_sizes": {str(i): b for p in parts for i, b in sorted(p[4])}}
+        ls = sorted(x for p in parts for x in p[5])
+        if ls:  # --loss_scale dynamic: member id -> current loss scale / updates skipped so far (overflowed steps)
+            rec["loss_scale"] = {str(i): s for i, s, _ in ls}
+            rec["skipped_steps"] = {str(i): k for i, _, k in ls}
         self._prev_exploit = self.exploit_time
         import json
         os.makedirs(self.savedata, exist_ok=True)

@@ -32,7 +32,11 @@ def get_dtype(name: str) -> torch.dtype:
     return DTYPE_MAP[name][0]
 
 
-def get_loss_scale(dtype: str, loss_scale: Optional[float]) -> float:
+def get_loss_scale(dtype: str, loss_scale):
+    """The loss scale of a run: the given positive number, "dynamic" (per-member dynamic scaling), or the dtype's
+    default (fp16: 128)."""
+    if loss_scale == "dynamic":
+        return "dynamic"
     if loss_scale is not None:
         return float(loss_scale)
     return float(DTYPE_MAP[dtype][1])
@@ -43,6 +47,20 @@ def _positive(v):
     if f <= 0:
         raise argparse.ArgumentTypeError("loss_scale should be a positive number.")
     return f
+
+
+def _loss_scale(v):
+    """--loss_scale: a positive number (static) or ``dynamic``."""
+    if isinstance(v, str) and v.strip().lower() == "dynamic":
+        return "dynamic"
+    return _positive(v)
+
+
+def _positive_int(v):
+    n = int(v)
+    if n < 1:
+        raise argparse.ArgumentTypeError("should be a positive integer.")
+    return n
 
 
 def _str2bool(v):
@@ -124,7 +142,13 @@ def build_parser(defaults: Optional[Dict[str, Any]] = None) -> argparse.Argument
     p.add_argument("--debug_steps", type=int, default=None, help="MNIST: steps per 'epoch' (reference used 10)")
     p.add_argument("--batch_size", type=int, default=None, help="override every member's batch_size")
     p.add_argument("--dtype", default="bf16", choices=list(DTYPE_MAP))
-    p.add_argument("--loss_scale", type=_positive, default=None)
+    p.add_argument("--loss_scale", type=_loss_scale, default=None,
+                   help="a positive number: static loss scaling (fp16 default 128); 'dynamic': per-member dynamic loss "
+                        "scaling -- a member whose gradients overflow skips that update and halves its scale, the "
+                        "scale doubles after --loss_scale_growth_steps clean steps (fp16 CIFAR ResNet v2 HIP step, "
+                        "or --backend torch)")
+    p.add_argument("--loss_scale_growth_steps", type=_positive_int, default=2000,
+                   help="--loss_scale dynamic: clean steps in a row after which a member's scale doubles")
     p.add_argument("--data_format", default="channels_last", choices=["channels_last"])
     p.add_argument("--backend", default="auto", choices=["auto", "hip", "torch"])
     p.add_argument("--hooks", default="",
@@ -177,6 +201,8 @@ class MainArgs(argparse.Namespace):
                 kw["data_dir"] = self.data_dir
             kw["dtype"] = self.dtype
             kw["loss_scale"] = get_loss_scale(self.dtype, self.loss_scale)
+            if kw["loss_scale"] == "dynamic":
+                kw["loss_scale_growth_steps"] = int(getattr(self, "loss_scale_growth_steps", 2000))
             kw["hooks"] = self.hooks
             kw["hook_every_n"] = self.log_every_n_steps
             kw["model_dir"] = self.savedata
@@ -249,6 +275,27 @@ def hip_deterministic(args) -> bool:
     return args.model in ("mnist", "cifar10", "imagenet") and dt in ("bf16", "fp32")
 
 
+def _check_dynamic_loss_scale(p, args) -> None:
+    """--loss_scale dynamic: the fp16 CIFAR ResNet v2 HIP step has the device-side path; --backend torch has the same
+    rule for every family.  Everything else is an error (bf16 needs no loss scaling; the fp32 HIP steps do not scale
+    the loss; the ImageNet HIP step's deterministic build accumulates gradients as int64 fixed point, where Inf is
+    not representable)."""
+    if args.model == "toy":
+        p.error("--loss_scale dynamic: the toy model has no loss scaling")
+    if args.backend == "torch":
+        return
+    if args.dtype == "bf16":
+        p.error("--loss_scale dynamic: bf16 needs no loss scaling (pass --backend torch to scale anyway)")
+    if args.dtype == "fp32" and args.backend == "hip":
+        p.error("--loss_scale dynamic with --dtype fp32: the fp32 HIP step does not scale the loss; use --backend "
+                "torch")
+    if args.dtype == "fp16" and args.model == "imagenet":
+        p.error("--loss_scale dynamic: the ImageNet HIP step has no dynamic loss scaling yet (its deterministic build "
+                "accumulates gradients in int64 fixed point, which cannot hold Inf); use --backend torch or a static "
+                "--loss_scale")
+    # fp32 with --backend auto and fp16 MNIST fall to the PyTorch path below, as with a static scale
+
+
 def parse_main_args(argv=None, defaults=None) -> MainArgs:
     p = build_parser(defaults)
     args = p.parse_args(argv, namespace=MainArgs())
@@ -256,6 +303,8 @@ def parse_main_args(argv=None, defaults=None) -> MainArgs:
         args.population_size = args.pop_size
     if args.resnet_version == 1 and args.dtype == "fp16":
         p.error("ResNet version 1 is not currently supported with fp16. Please use version 2 instead.")
+    if args.loss_scale == "dynamic":
+        _check_dynamic_loss_scale(p, args)
     if args.dtype == "fp32" and args.model in ("cifar10", "mnist", "imagenet"):
         # every family has an fp32 HIP step (engine/hip_f32.py, hip_mnist_f32.py, hip_imagenet_f32.py:
         # v_mfma_f32_16x16x4_f32, fp32 tensors); a static loss scale is a PyTorch-path feature

@@ -21,7 +21,8 @@ from typing import Any, Callable, Dict, List, Optional
 
 from .logger import get_benchmark_logger, log
 
-_TENSORS_TO_LOG = ("learning_rate", "cross_entropy", "train_accuracy")
+# (loss_scale / skipped_steps: present only in runs with --loss_scale dynamic)
+_TENSORS_TO_LOG = ("learning_rate", "cross_entropy", "train_accuracy", "loss_scale", "skipped_steps")
 
 
 class StepHook:

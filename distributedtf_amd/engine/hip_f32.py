@@ -28,7 +28,7 @@ import torch
 
 from .. import ops
 from .hip_imagenet import BnFinArgs, _register as _register_cg, xcd_order
-from .hip_step import HipBackend, HipPlan, _log2, _p, same_batches
+from .hip_step import HipBackend, HipPlan, _log2, _p
 
 c_void_p, c_int, c_long = ctypes.c_void_p, ctypes.c_int, ctypes.c_long
 CMAX = 64
@@ -141,12 +141,6 @@ class HipResNetF32Backend(HipBackend):
         self.ident[:, 0].fill_(1.0)
         self.ident[:, 3].fill_(1.0)
 
-    def on_params_changed(self, slots):
-        pass  # the kernels read the fp32 master rows directly
-
-    def shadow_weights(self):
-        return None
-
     @torch.no_grad()
     def infer(self, slot, x):
         p = self.eval_plan([slot], int(x.shape[0]))
@@ -158,25 +152,9 @@ class HipResNetF32Backend(HipBackend):
 
 class _F32Plan(HipPlan):
     def __init__(self, be: HipResNetF32Backend, slots: List[int], sizes: List[int], eval_mode: bool = False):
-        self.be, self.e = be, be.e
-        self.eval = bool(eval_mode)
-        e, dev, prog, cfg = be.e, be.dev, be.prog, be.cfg
-        self.slots, self.sizes = slots, sizes
-        N = sum(sizes)
-        self.N = N
-        img_slot, self.first = [], {}
-        for s, n in zip(slots, sizes):
-            self.first[s] = len(img_slot)
-            img_slot += [s] * n
-        self.img_slot = torch.tensor(img_slot, dtype=torch.int32, device=dev)
-        cnt = torch.zeros(e.capacity, dtype=torch.float32)
-        for s, n in zip(slots, sizes):
-            cnt[s] = float(n)
-        self.cnt = cnt.to(dev)
-        self.slots_t = torch.tensor(slots, dtype=torch.int32, device=dev)
-        self.slots_long = torch.tensor(slots, dtype=torch.long, device=dev)
+        self._init_members(be, slots, sizes, eval_mode)
+        e, dev, prog, cfg, N = be.e, be.dev, be.prog, be.cfg, self.N
         self.first_t = torch.tensor([self.first[s] for s in slots], dtype=torch.int32, device=dev)
-        self.loss_sel = torch.zeros(len(slots), dtype=torch.float32, device=dev)
         H = cfg.image_size
         self.H = H
         f32 = torch.float32
@@ -207,9 +185,6 @@ class _F32Plan(HipPlan):
         self.dlog = torch.zeros(N, cfg.num_classes, dtype=f32, device=dev)
         self.dfeat = torch.zeros(N, cin, dtype=f32, device=dev)
         self._tmp: Dict[tuple, torch.Tensor] = {}
-        self._keep = []
-        self.launches = []
-        self.graph = None
         if self.eval:
             nb = len(prog.bns)
             self.ev_coef = torch.zeros(nb, e.capacity, 4, CMAX, dtype=f32, device=dev)
@@ -554,22 +529,6 @@ class _F32Plan(HipPlan):
         self.head(self._head_args(False), 0)
 
     # ------------------------------------------------------------------------------------------------ execution
-    def load_batch(self, batches):
-        if same_batches(self, batches):
-            return
-        off = 0
-        for (x, y) in batches:
-            n = x.shape[0]
-            self.x_in[off:off + n].copy_(x.reshape(n, *self.x_in.shape[1:]), non_blocking=True)
-            self.labels[off:off + n].copy_(y, non_blocking=True)
-            off += n
-
-    def load_eval(self, x, y):
-        m, k = x.shape[0], len(self.slots)
-        shp = tuple(self.x_in.shape[1:])
-        self.x_in.view(k, m, *shp).copy_(x.reshape(1, m, *shp).expand(k, *([-1] * (len(shp) + 1))))
-        self.labels.view(k, m).copy_(y.reshape(1, m).expand(k, -1))
-
     def logits_of(self, slot):
         """Eval logits of ``slot``'s images from the head's features (dense on the host side of the graph)."""
         e, prog, cfg = self.e, self.be.prog, self.be.cfg
@@ -578,9 +537,6 @@ class _F32Plan(HipPlan):
                                                                                                self.CL)
         b = e.state[slot, prog.dense_b_off:prog.dense_b_off + cfg.num_classes]
         return self.feat[i0:i0 + n] @ W.t() + b
-
-    def run_eval(self):
-        self._run_eager()
 
 
 HipResNetF32Backend._plan_cls = _F32Plan

@@ -26,7 +26,7 @@ from typing import Dict, List
 import torch
 
 from .. import ops
-from .hip_step import HipBackend, HipPlan, _log2, _p, same_batches
+from .hip_step import HipBackend, HipPlan, _log2, _p
 
 c_void_p, c_int, c_long, c_float = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_float
 CMAX = 2048
@@ -314,15 +314,6 @@ class HipImageNetBackend(HipBackend):
             self.ident[:, 0].fill_(1.0)
             self.ident[:, 3].fill_(1.0)
 
-    def on_params_changed(self, slots):
-        slots = list(slots)
-        if slots:  # rows changed outside the optimizer (init, exploit import): refresh their bf16 shadow
-            e = self.e
-            self._rows = ops.shadow_refresh(e.state, self.shadow, slots, e.Pp, e.P)
-
-    def shadow_weights(self):
-        return self.shadow
-
     @torch.no_grad()
     def infer(self, slot, x):
         """Eval-mode logits of one member on the HIP forward kernels (moving BN statistics)."""
@@ -336,24 +327,8 @@ class HipImageNetBackend(HipBackend):
 
 class _ImageNetPlan(HipPlan):
     def __init__(self, be: HipImageNetBackend, slots: List[int], sizes: List[int], eval_mode: bool = False):
-        self.be, self.e = be, be.e
-        self.eval = bool(eval_mode)
-        e, dev, prog, cfg = be.e, be.dev, be.prog, be.cfg
-        self.slots, self.sizes = slots, sizes
-        N = sum(sizes)
-        self.N = N
-        img_slot, self.first = [], {}
-        for s, n in zip(slots, sizes):
-            self.first[s] = len(img_slot)
-            img_slot += [s] * n
-        self.img_slot = torch.tensor(img_slot, dtype=torch.int32, device=dev)
-        cnt = torch.zeros(e.capacity, dtype=torch.float32)
-        for s, n in zip(slots, sizes):
-            cnt[s] = float(n)
-        self.cnt = cnt.to(dev)
-        self.slots_t = torch.tensor(slots, dtype=torch.int32, device=dev)
-        self.slots_long = torch.tensor(slots, dtype=torch.long, device=dev)
-        self.loss_sel = torch.zeros(len(slots), dtype=be.loss.dtype, device=dev)
+        self._init_members(be, slots, sizes, eval_mode)
+        e, dev, prog, cfg, N = be.e, be.dev, be.prog, be.cfg, self.N
         bf = self._act_dtype()
         H = cfg.image_size
         self.H = H
@@ -413,8 +388,6 @@ class _ImageNetPlan(HipPlan):
         self.dlog = torch.zeros(N, NPAD_CLS, dtype=bf, device=dev)
         self.dfeat = torch.empty(N, cfg.final_size, dtype=torch.float32, device=dev)
         self._tmp: Dict[tuple, torch.Tensor] = {}
-        self._keep = []
-        self.launches = []
         if self.eval:
             nb = len(prog.bns)
             self.ev_coef = torch.zeros(nb, e.capacity, 4, CMAX, dtype=torch.float32, device=dev)
@@ -424,7 +397,6 @@ class _ImageNetPlan(HipPlan):
             self._build_eval_v1() if self.v1 else self._build_eval()
         else:
             self._build_v1() if self.v1 else self._build()
-        self.graph = None
 
     # ----------------------------------------------------------------------------------------- helpers
     def _act_dtype(self):
@@ -1170,29 +1142,6 @@ class _ImageNetPlan(HipPlan):
         self._hold(g)
         self.gap(g, 0)
         self.dense_head(False)
-
-    def load_eval(self, x, y):
-        """The same eval images for every member: [m, H, W, C] fp32 -> this plan's [members * m] input."""
-        m, k = x.shape[0], len(self.slots)
-        assert all(n == m for n in self.sizes)
-        shp = tuple(self.x_in.shape[1:])
-        self.x_in.view(k, m, *shp).copy_(x.reshape(1, m, *shp).expand(k, *([-1] * (len(shp) + 1))))
-        self.labels.view(k, m).copy_(y.reshape(1, m).expand(k, -1))
-
-    def run_eval(self):
-        assert self.eval
-        self._run_eager()
-
-    # ----------------------------------------------------------------------------------------- execution
-    def load_batch(self, batches):
-        if same_batches(self, batches):
-            return
-        off = 0
-        for (x, y) in batches:
-            n = x.shape[0]
-            self.x_in[off:off + n].copy_(x.reshape(n, *self.x_in.shape[1:]), non_blocking=True)
-            self.labels[off:off + n].copy_(y, non_blocking=True)
-            off += n
 
 
 HipImageNetBackend._plan_cls = _ImageNetPlan

@@ -100,12 +100,6 @@ class HipImageNetF32Backend(HipImageNetBackend):
         self.ident[:, 0].fill_(1.0)
         self.ident[:, 3].fill_(1.0)
 
-    def on_params_changed(self, slots):
-        pass
-
-    def shadow_weights(self):
-        return None
-
 
 class _ImageNetF32Plan(_ImageNetPlan):
     FOLD1_OK = False  # (the fp32 conv kernels are not exercised with the read-once BN1 fold)

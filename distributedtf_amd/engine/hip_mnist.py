@@ -24,14 +24,14 @@ member at once over chunks of the eval set (``evaluate_population``).
 from __future__ import annotations
 
 import ctypes
-from typing import List, Sequence
+from typing import List
 
 import numpy as np
 import torch
 
 from .. import ops
 from ..data.datasets import batch_len
-from .hip_step import HipBackend, PinnedStager, _p, advance_steps, run_captured, same_batches
+from .hip_step import HipBackend, HipPlan, PinnedStager, _p
 
 c_void_p, c_int, c_long, c_float = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_float
 
@@ -168,16 +168,6 @@ class HipMnistBackend(HipBackend):
         self.keep_probs = False
         self._last_plan = None
 
-    # engine hooks ----------------------------------------------------------------------------
-    def on_params_changed(self, slots):
-        slots = [s for s in slots]
-        if slots:
-            e = self.e
-            self._rows = ops.shadow_refresh(e.state, self.shadow, slots, e.Pp, e.P)
-
-    def shadow_weights(self):
-        return self.shadow
-
     def _upload_rng(self, v):
         if getattr(self, "_rng_stage", None) is None:
             self._rng_stage = PinnedStager(2, torch.int32)
@@ -209,38 +199,13 @@ class HipMnistBackend(HipBackend):
             out.append(torch.softmax(p.logits[f:f + n], dim=1))
         return out
 
-    @torch.no_grad()
-    def infer(self, slot, x):
-        """Eval-mode logits of one member on the HIP forward kernels (dropout off)."""
-        p = self.eval_plan([slot], int(x.shape[0]))
-        logits = p.want_logits()
-        p.load_eval(x, torch.zeros(x.shape[0], dtype=torch.int32, device=x.device))
-        p.run_eval()
-        return logits.clone()
 
-
-class _MnistPlan:
+class _MnistPlan(HipPlan):
     def __init__(self, be: HipMnistBackend, slots: List[int], sizes: List[int], eval_mode: bool = False):
-        self.be, self.e = be, be.e
-        self.eval = bool(eval_mode)
-        e, dev = be.e, be.dev
-        self.slots, self.sizes = slots, sizes
-        N = sum(sizes)
-        self.N = N
-        img_slot, self.first = [], {}
-        for s, n in zip(slots, sizes):
-            self.first[s] = len(img_slot)
-            img_slot += [s] * n
-        self.img_slot = torch.tensor(img_slot, dtype=torch.int32, device=dev)
-        cnt = torch.zeros(e.capacity, dtype=torch.float32)
-        for s, n in zip(slots, sizes):
-            cnt[s] = float(n)
-        self.cnt = cnt.to(dev)
-        self.slots_t = torch.tensor(slots, dtype=torch.int32, device=dev)
-        self.slots_long = torch.tensor(slots, dtype=torch.long, device=dev)
-        self.loss_sel = torch.zeros(len(slots), dtype=be.loss.dtype, device=dev)
+        self._init_members(be, slots, sizes, eval_mode)
+        e, dev, N = be.e, be.dev, self.N
         bf = torch.bfloat16
-        self.x = torch.zeros(N, 28, 28, dtype=torch.float32, device=dev)
+        self.x_in = torch.zeros(N, 28, 28, dtype=torch.float32, device=dev)
         self.labels = torch.zeros(N, dtype=torch.int32, device=dev)
         self.p1 = torch.empty(N, 196, 32, dtype=bf, device=dev)
         self.am1 = torch.empty(N, 196, 32, dtype=torch.uint8, device=dev)
@@ -256,7 +221,7 @@ class _MnistPlan:
         self.logits = None
         o = be.offs
         a = MnistArgs()
-        a.x, a.labels, a.img_slot = _p(self.x), _p(self.labels), _p(self.img_slot)
+        a.x, a.labels, a.img_slot = _p(self.x_in), _p(self.labels), _p(self.img_slot)
         a.params, a.p_mstride = _p(e.state), e.S
         a.grads, a.g_mstride = _p(e.grads), e.Pp
         a.shadow, a.s_mstride = _p(be.shadow), e.Pp
@@ -274,19 +239,15 @@ class _MnistPlan:
         a.train = 0 if self.eval else 1
         if self.eval:  # counts accumulate over the eval chunks in the plan's own buffers
             a.loss, a.correct = _p(self.ev_acc[1]), _p(self.ev_acc[0])
-        self.args = a
+        self.args, self._copies = a, []  # the template: every launch reads its own copy over its own work table
         # work lists (img0, nimg, 0, slot): image chunks of one member.  Deterministic build: ONE chunk per member
         # for every launch that adds into per-member accumulators (dense / conv weight gradients, bias gradients,
         # loss, correct count) -- each address then receives a single add onto zero, and every partial sum is
         # formed in a fixed order inside its workgroup, so the step replays bitwise (the GEMMs own their tiles)
         det = ops.build_deterministic()
         whole = 1 << 30
-        self.w_fwd = self._chunks(max(1, -(-N // 512)))
-        self.w_head = self._chunks(whole if det else 16)
-        self.w_dgrad = self._chunks(max(1, -(-N // 512)))
-        self.w_c2w = self._chunks(whole if det else max(4, -(-N * 5 // 320)))
-        self.w_c1w = self._chunks(whole if det else max(4, -(-N // 256)))
-        Pp, S = e.Pp, e.S
+        w_fwd = self._chunks(max(1, -(-N // 512)))
+        Pp = e.Pp
         d1 = o["dense1_w"]
         fwd, dgr, wgr = [], [], []
         for s, n in zip(slots, sizes):
@@ -294,84 +255,46 @@ class _MnistPlan:
             fwd.append((f * 3136, s * Pp + d1, f * 1024, n, 1024, 3136))     # Z = P2 W^T
             dgr.append((f * 1024, s * Pp + d1, f * 3136, n, 3136, 1024))     # dP2 = dZ W
             wgr.append((f * 1024, f * 3136, s * Pp + d1, 1024, 3136, n))     # dW += dZ^T P2
-        self.g_fwd = GroupedGemm(self.p2, be.shadow, self.z, 3136, 3136, 1024, fwd, False, False, GEMM_OUT_F32, dev)
+        L = ops.lib()
         if not self.eval:
-            self.g_dgr = GroupedGemm(self.dz, be.shadow, self.dp2, 1024, 3136, 3136, dgr, False, True, GEMM_OUT_BF16,
-                                     dev)
-            self.g_wgr = GroupedGemm(self.dz, self.p2, e.grads, 1024, 3136, 3136, wgr, True, True, GEMM_OUT_ACC, dev)
-        self.graph = None
+            self._add(L.dtf_mnist_wd_prep, ctypes.byref(self._args()), _p(self.slots_t), len(slots))
+            self._add("zero", be.loss)
+            self._add("zero", be.correct)
+        # forward (eval -- mnist_model.py:167-172 ``mnist_classifier.evaluate`` -- stops after the head, dropout off)
+        self._launch(L.dtf_mnist_conv1, n=N)
+        self._launch(L.dtf_mnist_conv2_fwd, w_fwd)
+        self._gemm(GroupedGemm(self.p2, be.shadow, self.z, 3136, 3136, 1024, fwd, False, False, GEMM_OUT_F32, dev))
+        self._launch(L.dtf_mnist_head, self._chunks(whole if det else 16))
+        if self.eval:
+            return
+        self._gemm(GroupedGemm(self.dz, be.shadow, self.dp2, 1024, 3136, 3136, dgr, False, True, GEMM_OUT_BF16, dev))
+        self._gemm(GroupedGemm(self.dz, self.p2, e.grads, 1024, 3136, 3136, wgr, True, True, GEMM_OUT_ACC, dev))
+        self._launch(L.dtf_mnist_conv2_dgrad, self._chunks(max(1, -(-N // 512))))
+        self._launch(L.dtf_mnist_conv2_wgrad, self._chunks(whole if det else max(4, -(-N * 5 // 320))))
+        self._launch(L.dtf_mnist_conv1_wgrad, self._chunks(whole if det else max(4, -(-N // 256))))
+        self._add("optim", None)
+        self._add("step", None)
 
-    # ---- eval (mnist_model.py:167-172 ``mnist_classifier.evaluate``: dropout off)
+    def _args(self, work=None):
+        a = MnistArgs.from_buffer_copy(self.args)
+        a.work = _p(work)
+        self._copies.append(self._hold(a))
+        self._hold(work)
+        return a
+
+    def _launch(self, fn, work=None, n=None):
+        self._add(fn, ctypes.byref(self._args(work)), n if work is None else work.shape[0])
+
+    def _gemm(self, g):
+        self._hold(g)
+        self._add(ops.lib().dtf_gemm_bf16, ctypes.byref(g.args), g.mode, g.nwork)
+
     def want_logits(self):
         if self.logits is None:
             self.logits = torch.zeros(self.N, 10, dtype=torch.float32, device=self.be.dev)
-            self.args.logits_out = _p(self.logits)
+            for a in self._copies:  # (the head reads it; the launches keep seeing one set of arguments)
+                a.logits_out = _p(self.logits)
         return self.logits
-
-    def load_eval(self, x, y):
-        m, k = x.shape[0], len(self.slots)
-        assert all(n == m for n in self.sizes)
-        self.x.view(k, m, 28, 28).copy_(x.reshape(1, m, 28, 28).expand(k, -1, -1, -1))
-        self.labels.view(k, m).copy_(y.reshape(1, m).expand(k, -1))
-
-    def run_eval(self):
-        assert self.eval
-        L, st = ops.lib(), ops.stream()
-        self._launch(L.dtf_mnist_conv1, n=self.N)
-        self._launch(L.dtf_mnist_conv2_fwd, self.w_fwd)
-        self.g_fwd.launch(st)
-        self._launch(L.dtf_mnist_head, self.w_head)
-
-    def _chunks(self, chunk):
-        items = []
-        for s, n in zip(self.slots, self.sizes):
-            f = self.first[s]
-            for i in range(0, n, chunk):
-                items.append([f + i, min(chunk, n - i), 0, s])
-        return torch.tensor(items, dtype=torch.int32, device=self.be.dev)
-
-    def load_batch(self, batches):
-        if same_batches(self, batches):
-            return
-        off = 0
-        for (x, y) in batches:
-            n = x.shape[0]
-            self.x[off:off + n].copy_(x.reshape(n, 28, 28), non_blocking=True)
-            self.labels[off:off + n].copy_(y, non_blocking=True)
-            off += n
-
-    def _launch(self, fn, work=None, n=None):
-        a = self.args
-        if work is not None:
-            a.work = _p(work)
-            n = work.shape[0]
-        err = fn(ctypes.byref(a), n, ops.stream())
-        if err != 0:
-            raise RuntimeError("%s launch failed: %d" % (getattr(fn, "__name__", "mnist kernel"), err))
-
-    def _run_eager(self):
-        be, e, L = self.be, self.e, ops.lib()
-        st = ops.stream()
-        err = L.dtf_mnist_wd_prep(ctypes.byref(self.args), _p(self.slots_t), len(self.slots), st)
-        if err:
-            raise RuntimeError("mnist_wd_prep failed: %d" % err)
-        be.loss.zero_()
-        be.correct.zero_()
-        self._launch(L.dtf_mnist_conv1, n=self.N)
-        self._launch(L.dtf_mnist_conv2_fwd, self.w_fwd)
-        self.g_fwd.launch(st)
-        self._launch(L.dtf_mnist_head, self.w_head)
-        self.g_dgr.launch(st)
-        self.g_wgr.launch(st)
-        self._launch(L.dtf_mnist_conv2_dgrad, self.w_dgrad)
-        self._launch(L.dtf_mnist_conv2_wgrad, self.w_c2w)
-        self._launch(L.dtf_mnist_conv1_wgrad, self.w_c1w)
-        e.dp_sync_grads(self.slots)  # data-parallel member groups only (no-op otherwise)
-        ops.fused_optimizer(e.state, e.grads, e.hyper, e.Pp, e.P, e.n_reg, shadow=be.shadow, zero_grads=True)
-        advance_steps(e, self.slots_long, self.slots_t, be.loss, self.loss_sel)
-
-    def run(self):
-        run_captured(self)
 
 
 HipMnistBackend._plan_cls = _MnistPlan

@@ -35,7 +35,7 @@ import torch
 from .. import ops
 from .hip_f32 import F32Args, TP, WG_CHUNK, _register as _register_f32
 from .hip_mnist import HipMnistBackend, MnistArgs, _register as _register_mnist
-from .hip_step import HipPlan, _p, same_batches
+from .hip_step import HipPlan, _p
 
 c_void_p, c_int, c_long = ctypes.c_void_p, ctypes.c_int, ctypes.c_long
 
@@ -87,41 +87,19 @@ class HipMnistF32Backend(HipMnistBackend):
         self.gacc = torch.zeros(cap, e.Pp, dtype=torch.int64, device=self.dev) if self.det else None
         self.loss_sink = torch.zeros(cap, dtype=torch.float32, device=self.dev) if self.det else None
         self.loss64_sink = torch.zeros(cap, dtype=torch.int64, device=self.dev) if self.det else None
-        self.shadow = None
-
-    def on_params_changed(self, slots):
-        pass  # the kernels read the fp32 master rows directly
-
-    def shadow_weights(self):
-        return None
+        self.shadow = None  # the kernels read the fp32 master rows directly
 
 
 class _MnistF32Plan(HipPlan):
     def __init__(self, be: HipMnistF32Backend, slots: List[int], sizes: List[int], eval_mode: bool = False):
-        self.be, self.e = be, be.e
-        self.eval = bool(eval_mode)
-        e, dev = be.e, be.dev
-        self.slots, self.sizes = slots, sizes
-        N = sum(sizes)
-        self.N = N
-        img_slot, self.first = [], {}
-        for s, n in zip(slots, sizes):
-            self.first[s] = len(img_slot)
-            img_slot += [s] * n
-        self.img_slot = torch.tensor(img_slot, dtype=torch.int32, device=dev)
-        cnt = torch.zeros(e.capacity, dtype=torch.float32)
-        for s, n in zip(slots, sizes):
-            cnt[s] = float(n)
-        self.cnt = cnt.to(dev)
-        self.slots_t = torch.tensor(slots, dtype=torch.int32, device=dev)
-        self.slots_long = torch.tensor(slots, dtype=torch.long, device=dev)
-        self.loss_sel = torch.zeros(len(slots), dtype=torch.float32, device=dev)
+        self._init_members(be, slots, sizes, eval_mode)
+        e, dev, N = be.e, be.dev, self.N
         f32 = torch.float32
 
         def t(*shape, dtype=f32):
             return torch.empty(*shape, dtype=dtype, device=dev)
 
-        self.x = torch.zeros(N, 28, 28, dtype=f32, device=dev)
+        self.x_in = torch.zeros(N, 28, 28, dtype=f32, device=dev)
         self.labels = torch.zeros(N, dtype=torch.int32, device=dev)
         self.x4 = t(N, 28, 28, 4)
         self.h1, self.p1, self.am1 = t(N, 28, 28, 32), t(N, 14, 14, 32), t(N, 14, 14, 32, dtype=torch.uint8)
@@ -132,9 +110,6 @@ class _MnistF32Plan(HipPlan):
             self.dp1, self.dh1 = t(N, 14, 14, 32), t(N, 28, 28, 32)
         self.ev_acc = torch.zeros(2, e.capacity, dtype=f32, device=dev)  # eval: [correct, summed CE]
         self.logits = None
-        self._keep = []
-        self.launches = []
-        self.graph = None
         o = be.offs
         a = MnistArgs()
         a.labels, a.img_slot = _p(self.labels), _p(self.img_slot)
@@ -158,14 +133,6 @@ class _MnistF32Plan(HipPlan):
         self._build()
 
     # ------------------------------------------------------------------------------------------------ helpers
-    def _chunks(self, chunk):
-        items = []
-        for s, n in zip(self.slots, self.sizes):
-            f = self.first[s]
-            for i in range(0, n, chunk):
-                items.append([f + i, min(chunk, n - i), 0, s])
-        return torch.tensor(items, dtype=torch.int32, device=self.be.dev)
-
     def _f32args(self, w_off, Hi, Ci, wci, Ho, Co, k, pad):
         e = self.e
         a = F32Args()
@@ -245,7 +212,7 @@ class _MnistF32Plan(HipPlan):
     # ------------------------------------------------------------------------------------------------ program
     def _forward(self):
         o, N = self.be.offs, self.N
-        self._add(ops.lib().dtf_mnist_f32_prep, _p(self.x), _p(self.x4), N * 784)
+        self._add(ops.lib().dtf_mnist_f32_prep, _p(self.x_in), _p(self.x4), N * 784)
         self.conv(self.x4, self.h1, o["conv1_w"], 28, 4, 1, 28, 32, 5, 2)
         self.pool(self.h1, self.p1, self.am1, o["conv1_b"], 28, 32)
         self.conv(self.p1, self.h2, o["conv2_w"], 14, 32, 32, 14, 64, 5, 2)
@@ -281,26 +248,6 @@ class _MnistF32Plan(HipPlan):
             self.logits = torch.zeros(self.N, 10, dtype=torch.float32, device=self.be.dev)
             self.head_args.logits_out = _p(self.logits)
         return self.logits
-
-    def load_eval(self, x, y):
-        m, k = x.shape[0], len(self.slots)
-        assert all(n == m for n in self.sizes)
-        self.x.view(k, m, 28, 28).copy_(x.reshape(1, m, 28, 28).expand(k, -1, -1, -1))
-        self.labels.view(k, m).copy_(y.reshape(1, m).expand(k, -1))
-
-    def load_batch(self, batches):
-        if same_batches(self, batches):
-            return
-        off = 0
-        for (x, y) in batches:
-            n = x.shape[0]
-            self.x[off:off + n].copy_(x.reshape(n, 28, 28), non_blocking=True)
-            self.labels[off:off + n].copy_(y, non_blocking=True)
-            off += n
-
-    def run_eval(self):
-        assert self.eval
-        self._run_eager()
 
 
 HipMnistF32Backend._plan_cls = _MnistF32Plan

@@ -35,7 +35,7 @@ import torch
 from .. import ops
 from ..data.datasets import IndexBatch, batch_len
 from ..models.resnet import BN_EPS
-from .hip_step import (HipBackend, LossRing, PinnedStager, _LIVE_GRAPH_PLANS, _p, advance_steps,  # noqa: F401
+from .hip_step import (HipBackend, HipPlan, LossRing, PinnedStager, _LIVE_GRAPH_PLANS, _p, advance_steps,  # noqa: F401
                        graph_state, note_step_advanced, release_graphs, run_captured, run_optimizer, same_batches,
                        upload_hyper)
 
@@ -393,13 +393,7 @@ class HipResNetBackend(HipBackend):
         self.loss = self.zbuf[nst:nst + cap]
         self.correct = self.zbuf[nst + cap:]
 
-    # --- engine hooks --------------------------------------------------------------
-    def on_params_changed(self, slots):
-        pass  # weight_prep runs at the start of every step (inside the graph)
-
-    def shadow_weights(self):
-        return None
-
+    # (no shadow: weight_prep writes the bf16 weight layouts at the start of every step, inside the graph)
     def st_f(self, bn):
         return self.stats[0, bn]
 
@@ -480,63 +474,34 @@ class HipResNetBackend(HipBackend):
             return p.loss_view()[p.slot_index(slots)]
         return p.loss_view()
 
-    @torch.no_grad()
-    def infer(self, slot, x):
-        """Eval-mode logits of one member on the HIP forward kernels (moving BN statistics)."""
-        p = self.eval_plan([slot], int(x.shape[0]))
-        logits = p.want_logits()
-        p.load_eval(x, torch.zeros(x.shape[0], dtype=torch.int32, device=x.device))
-        p.run_eval()
-        return logits.clone()
 
-
-class _StepPlan:
+class _StepPlan(HipPlan):
     """Buffers + prebuilt launch list for one batch composition (slots, per-member sizes)."""
 
     def __init__(self, be: HipResNetBackend, slots: List[int], sizes: List[int], src=None, eval_mode=False,
                  elastic_cap=None):
-        self.be = be
-        e = be.e
-        self.e = e
-        self.slots = slots
         # elastic plan: buffers / layout for elastic_cap images per member, the real sizes live in self.cnt and
         # the work tables are rebuilt from them on the device at the start of every step (work_gen_kernel)
         self.elastic = bool(elastic_cap) and not eval_mode
         self.real_sizes = list(sizes)
         if self.elastic:
             sizes = [int(elastic_cap)] * len(slots)
-        self.sizes = sizes
-        self._wgen = []
-        self.eval = bool(eval_mode)
-        self._grab = None  # a list while the launches of a combined multi-role launch are collected (_add)
-        dev = be.dev
+        self._init_members(be, slots, sizes, eval_mode, counts=self.real_sizes)
+        e, dev, N = be.e, be.dev, self.N
         L = be.L
         prog = L.prog
         cfg = L.cfg
-        N = sum(sizes)
-        self.N = N
-        img_slot = []
-        self.first = {}
-        for s, n in zip(slots, sizes):
-            self.first[s] = len(img_slot)
-            img_slot += [s] * n
-        self.img_slot = torch.tensor(img_slot, dtype=torch.int32, device=dev)
-        cnt = torch.zeros(e.capacity, dtype=torch.float32)
-        for s, n in zip(slots, sizes):
-            cnt[s] = float(n)
-        self.cnt = cnt.to(dev)
+        self._wgen, self._elastic_red = [], {}  # elastic work tables and the slab-reduction tables over them
+        self._grab = None  # a list while the launches of a combined multi-role launch are collected (_add)
+        self._cnt_stage = self._rng_stage = None  # pinned stagers of set_sizes / the index-batch rng (made on use)
+        self._stamp_n, self.stamp_rows = {"fwd": 0, "fused": 0}, []  # DTF_STAMP diagnostic rows (_stamp_row)
+        self._det_rows = self.slab_buf = None
+        self._slot_index = {}
         # uniform population: work items of the stage kernels computed from blockIdx (ConvArgs.u_items)
         self.uniform = (len(set(sizes)) == 1 and list(slots) == list(range(len(slots))) and not self.elastic
                         and not be.det)
         if self.elastic:
-            for s, n in zip(slots, self.real_sizes):
-                cnt[s] = float(n)
-            self.cnt = cnt.to(dev)
             self.first_t = torch.tensor([self.first[s] for s in slots], dtype=torch.int32, device=dev)
-            self._cnt_stage = None
-        self.slots_t = torch.tensor(slots, dtype=torch.int32, device=dev)
-        self.slots_long = torch.tensor(slots, dtype=torch.long, device=dev)
-        self.loss_sel = torch.zeros(len(slots), dtype=be.loss.dtype, device=dev)
         self.ring = LossRing(len(slots), dev) if (dev.type == "cuda" and not eval_mode and len(slots) <= 1024) else None
         H = cfg.image_size
         self.x_in = torch.zeros(N, H, H, 3, dtype=torch.float32, device=dev)
@@ -573,6 +538,8 @@ class _StepPlan:
             if self.v1:
                 self.hb.append(act("hb", hw_o, ca.cout))
             hw = hw_o
+        self._work_cache, self._uniform_geo = {}, {}
+        self._pending_slab = None  # (slab ptr, reduce table, C, grad offset) of the last fused launch
         if self.eval:
             nb = len(prog.bns)
             cap = e.capacity
@@ -581,11 +548,7 @@ class _StepPlan:
             self.ev_sink = torch.zeros(cap, be.nrep, 128, dtype=torch.float32, device=dev)
             self.ev_acc = torch.zeros(2, cap, dtype=torch.float32, device=dev)  # [correct, summed mean CE] per slot
             self.logits = None  # [N, ncls] fp32 when requested (tests)
-            self._work_cache, self._uniform_geo = {}, {}
-            self.launches = []
-            self._pending_slab = None
             self._build_eval()
-            self.graph = None
             return
         # backward temporaries, one set per resolution
         self.tmp = {}
@@ -605,8 +568,6 @@ class _StepPlan:
                 self.pd[id(blk)] = torch.empty(N, hw, hw, ci, dtype=ops.act_dtype(), device=dev)
             hw //= blk.stride
         self.dfeat = torch.zeros(N, cfg.final_size, dtype=torch.float32, device=dev)
-        self._work_cache = {}
-        self._uniform_geo = {}
         # Small population (<= SMALL_POP_MAX members of a v2 net on the GPU, release build): the members leave CUs
         # idle, so every dgrad-role workgroup takes a single (image, band) iteration and every width defers its wgrad
         # (the deterministic build never switches kernel families with the population size: a member's reduction
@@ -623,8 +584,6 @@ class _StepPlan:
         large = DEFER_MID_CS if (len(slots) <= DEFER_MID_POP and not be.det) else DEFER_LARGE_CS
         self.defer_cs = {16, 32, 64} if self.small_pop else (set(large) if v2gpu else set())
         self._wg_jobs = {}  # (C, wgrad dY mode) -> [(ConvArgs, work table, grad offset)]
-        self.launches = []
-        self._pending_slab = None  # (slab ptr, reduce table, C, grad offset) of the last fused launch
         self._slab_flip = 0
         # C = 64 dW slabs reduced together by ONE launch after the backward (instead of 17 small reductions)
         self._deferred = []  # (slab, reduce table, grad offset, C): reduced by one launch per C after the backward
@@ -637,7 +596,6 @@ class _StepPlan:
             "every dW slab must be reduced before the optimizer"
         if self.elastic:
             self._work_gen_launch()
-        self.graph = None
 
     # -------------------------------------------------------------------- work lists
     def _work_iters(self, bands, n_wg, det_per=None):
@@ -701,18 +659,17 @@ class _StepPlan:
         assert len(host) == per * len(self.slots) * rows
         w = torch.tensor(host, dtype=torch.int32, device=self.be.dev)
         self._wgen.append((w, per, bands, min_chunk, int(split), prop))
-        self.__dict__.setdefault("_wgen_params", {})[w.data_ptr()] = (per, bands, min_chunk)
         return w
 
     def _work_gen_launch(self):
         """First launch of an elastic step: regenerate every work table from the per-member sizes (self.cnt)."""
         descs = (WorkGenDesc * len(self._wgen))()
-        red = getattr(self, "_elastic_red", {})
+        red = self._elastic_red
         for i, (w, per, bands, mc, sp, prop) in enumerate(self._wgen):
             # the slab-reduction table over this work table (one per member), rewritten with it every step
             descs[i] = WorkGenDesc(w.data_ptr(), _p(red.get(w.data_ptr())), per, bands, mc, sp, prop, 0)
         dt = torch.frombuffer(bytearray(bytes(descs)), dtype=torch.uint8).to(self.be.dev)
-        self._keep(dt)
+        self._hold(dt)
         self.launches.insert(0, (ops.lib().dtf_work_gen, (_p(dt), len(self._wgen), _p(self.slots_t),
                                                           _p(self.first_t), len(self.slots), _p(self.cnt))))
 
@@ -758,10 +715,8 @@ class _StepPlan:
             items = []
             per = DET_WG_PER_MEMBER
             for s, n in zip(self.slots, self.sizes):
-                f = self.first[s]
-                chunk = max(1, -(-n // per))
-                rows = [[f + i, min(chunk, n - i), 0, s] for i in range(0, n, chunk)]
-                items += rows + [[f, 0, 0, s]] * (per - len(rows))
+                rows = self._chunk_rows(s, n, max(1, -(-n // per)))
+                items += rows + [[self.first[s], 0, 0, s]] * (per - len(rows))
             w = torch.tensor(items, dtype=torch.int32, device=self.be.dev)
             self._work_cache[key] = w
         return w
@@ -773,14 +728,8 @@ class _StepPlan:
             w = self._elastic_table(max(1, target_items // max(1, len(self.slots))), 1, min_chunk)
             self._work_cache[key] = w
         if w is None:
-            items = []
             per_member = max(1, target_items // max(1, len(self.slots)))
-            for s, n in zip(self.slots, self.sizes):
-                chunk = max(min_chunk, -(-n // per_member))
-                f = self.first[s]
-                for i in range(0, n, chunk):
-                    items.append([f + i, min(chunk, n - i), 0, s])
-            w = torch.tensor(items, dtype=torch.int32, device=self.be.dev)
+            w = self._chunks(lambda n: max(min_chunk, -(-n // per_member)))
             self._work_cache[key] = w
         return w
 
@@ -806,7 +755,7 @@ class _StepPlan:
         if self._grab is not None:
             self._grab.append((fn, args))  # collected for a combined multi-role launch
             return
-        self.launches.append((fn, args))
+        super()._add(fn, *args)
 
     def _conv_fwd(self, ci, x, y, stats_bn, in_bn, res=None):
         be, L = self.be, self.be.L
@@ -856,7 +805,7 @@ class _StepPlan:
         else:
             self._add(lib.dtf_conv_fwd, ctypes.byref(a), cin, c.cout, c.stride, c.k, mode, int(res is not None),
                       int(stats_bn is not None), work.shape[0], lds)
-        self._keep(a)
+        self._hold(a)
 
     def _conv_dgrad(self, ci, dy, y, Hi, mode, epi, dy2=None, in_bn=None, res=None, xm=None, ep_bn=None):
         be, L = self.be, self.be.L
@@ -892,7 +841,7 @@ class _StepPlan:
         lds = 2304 + 2 * tsz * 2
         lib = ops.lib()
         self._add(lib.dtf_conv_dgrad, ctypes.byref(a), c.cin, c.cout, S, K, mode, epi, work.shape[0], lds)
-        self._keep(a)
+        self._hold(a)
 
     @staticmethod
     def _trans_multi(ca_spec):
@@ -964,7 +913,7 @@ class _StepPlan:
             a.slab = _p(self._layer_slab(work.shape[0] * kel))
             self._deferred_dense.append((a.slab, self._slab_table(work), c.off, kel))
         self._add(lib.dtf_conv_wgrad, ctypes.byref(a), cin, c.cout, c.stride, c.k, mode_x, mode_dy, work.shape[0], lds)
-        self._keep(a)
+        self._hold(a)
 
     def _conv_bwd_fused(self, ci, dy, dz_out, x, mode_dy, dy2=None, dy_bn=None, x_bn=None, res=None, ident_x=False,
                         dy3=None, dy_out=None, chain_bn=None, chain_h=None):
@@ -1035,7 +984,7 @@ class _StepPlan:
         epi = int(res is not None) | (2 if ident_x else 0) | (8 if chain_bn is not None else 0)
         a.cin_real = self._stamp_row("fused", "fused C=%d mdy=%d epi=%d" % (C, mode_dy, epi))
         self._add(lib.dtf_conv_bwd_fused, ctypes.byref(a), C, mode_dy, epi, work.shape[0] + n_red, lds)
-        self._keep(a)
+        self._hold(a)
         red = self._slab_table(work)
         if C == 64:
             self._deferred.append((a.slab, red, c.off, 64))
@@ -1093,7 +1042,7 @@ class _StepPlan:
         a.cin_real = self._stamp_row("fused", "fused-dg C=%d mdy=%d epi=%d" % (C, mode_dy, epi))
         tsz = ((rows_dg + 2) * _wpitch(C) * _cpad(C) + 8 + 63) // 64 * 64
         self._add(ops.lib().dtf_conv_bwd_dg, ctypes.byref(a), C, mode_dy, epi, rows_dg, a.n_main, 2304 + 2 * tsz * 2)
-        self._keep(a)
+        self._hold(a)
         # ---- wgrad job (the same staging of dY / x over 8-row bands)
         if dy_out is not None or mode_dy == 0:
             wmode, dy, dy2, dy_bn = 0, dy_out if dy_out is not None else dy, None, None
@@ -1131,15 +1080,13 @@ class _StepPlan:
             arr = (ConvArgs * len(arr_l))(*arr_l)
             jt = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(self.be.dev)
             mt = torch.tensor(wmap, dtype=torch.int32, device=self.be.dev)
-            self._keep(jt)
-            self._keep(mt)
+            self._hold(jt)
+            self._hold(mt)
             self._add(lib.dtf_conv_wgrad_all, _p(jt), _p(mt), len(wmap), cset, lds)
         self._wg_jobs = {}
 
     def _fresh_like(self, t):
-        u = torch.empty_like(t)
-        self._keep(u)
-        return u
+        return self._hold(torch.empty_like(t))
 
     def _piggyback(self, pend):
         """Reduce the previous launch's C = 16 / 32 slabs inside the next backward launch when that adds few
@@ -1172,8 +1119,8 @@ class _StepPlan:
             bmax = max(bmax, min(-(-kel // 32), DENSE_REDUCE_BLOCKS))
         st = torch.frombuffer(bytearray(bytes(sj)), dtype=torch.uint8).to(self.be.dev)
         dt = torch.frombuffer(bytearray(bytes(dj)), dtype=torch.uint8).to(self.be.dev)
-        self._keep(st)
-        self._keep(dt)
+        self._hold(st)
+        self._hold(dt)
         self._add(ops.lib().dtf_slab_reduce_all, _p(st), len(self._deferred), _p(dt), len(self._deferred_dense),
                   nmax, bmax, _p(self.e.grads), self.e.Pp)
         self._deferred, self._deferred_dense = [], []
@@ -1240,13 +1187,11 @@ class _StepPlan:
         self._deferred_dense.append((ha.slab_b, red, prog.dense_b_off, ncls))
 
     def _layer_slab(self, n):
-        t = torch.empty(max(n, 1), dtype=torch.float32, device=self.be.dev)
-        self._keep(t)
-        return t
+        return self._hold(torch.empty(max(n, 1), dtype=torch.float32, device=self.be.dev))
 
     def _slab(self, n):
         """The plan's two ping-pong slab buffers (sized once for the largest fused layer)."""
-        if getattr(self, "slab_buf", None) is None:
+        if self.slab_buf is None:
             self.slab_buf = [torch.empty(max(n, 1), dtype=torch.float32, device=self.be.dev) for _ in range(2)]
         assert self.slab_buf[0].numel() >= n, "slab must be sized once per plan"
         return self.slab_buf
@@ -1254,7 +1199,7 @@ class _StepPlan:
     def _slab_table(self, work):
         """(first wg, n wgs, 0, slot) per member of a work-item array grouped by member.  An elastic work table's rows
         per member change with the batch sizes: its table is shared and rewritten on the device by work_gen."""
-        red = self.__dict__.setdefault("_elastic_red", {})
+        red = self._elastic_red
         if work.data_ptr() in red:
             return red[work.data_ptr()]
         w = work.cpu().tolist()
@@ -1265,7 +1210,7 @@ class _StepPlan:
             else:
                 rows.append([i, 1, 0, it[3]])
         t = torch.tensor(rows, dtype=torch.int32, device=self.be.dev)
-        self._keep(t)
+        self._hold(t)
         if self.elastic and any(wg[0].data_ptr() == work.data_ptr() for wg in self._wgen):
             assert len(rows) == len(self.slots), "elastic slab table: one row per member"
             red[work.data_ptr()] = t
@@ -1273,17 +1218,70 @@ class _StepPlan:
 
     def _stamp_row(self, kind, label=""):
         """Row of the DTF_STAMP diagnostic buffer for the next launch of ``kind`` (fwd: 0.., fused: 64..)."""
-        if not hasattr(self, "_stamp_n"):
-            self._stamp_n = {"fwd": 0, "fused": 0}
         row = self._stamp_n[kind] + (64 if kind == "fused" else 0)
         self._stamp_n[kind] += 1
-        self.stamp_rows = getattr(self, "stamp_rows", []) + [(row, label)]
+        self.stamp_rows.append((row, label))
         return row
 
-    def _keep(self, obj):
-        if not hasattr(self, "_keepalive"):
-            self._keepalive = []
-        self._keepalive.append(obj)
+    def _step_prologue(self):
+        """First launches of a step or an eval chunk: the members' bf16 weight layouts -- the training step's launch
+        also zeroes the statistic accumulators, losses and correct counts (one buffer) --, an eval chunk's moving
+        statistics in accumulator form, and the packed input."""
+        be, e, L = self.be, self.e, self.be.L
+        lib = ops.lib()
+        nslots = len(self.slots)
+        zero = (None, 0) if self.eval else (_p(be.zbuf), be.zbuf.numel())
+        self._add(lib.dtf_weight_prep, _p(e.state), e.S, _p(be.conv_table_t), len(L.conv_table), _p(self.slots_t),
+                  nslots, _p(be.wf), _p(be.wd), L.wtot, *zero)
+        if self.eval:
+            self._add(lib.dtf_bn_eval_stats, _p(e.state), e.S, 3 * e.Pp, _p(be.bn_table_t), len(L.bn_table),
+                      _p(self.ev_stats), be.stats_bn_stride, _p(self.slots_t), nslots, _p(self.cnt))
+        if self.src is not None:
+            self._add("augment", None)  # gather + pad/crop/flip + standardize + bf16 pack (data.hip)
+        else:
+            self._add(lib.dtf_prep_input, _p(self.x_in), _p(self.xin16), self.N * L.cfg.image_size ** 2, 3)
+
+    def _step_epilogue(self):
+        """Last launches of a training step: the outstanding dW slab reductions, the BN parameter gradients from the
+        backward reductions (+ moving statistics), the optimizer over every member row (+ zero grads), the step
+        counters."""
+        be, e, L = self.be, self.e, self.be.L
+        self._flush_slab()
+        self._flush_deferred()
+        self._add(ops.lib().dtf_bn_step_end, _p(e.state), e.S, 3 * e.Pp, _p(be.bn_table_t), len(L.bn_table),
+                  _p(be.stats[0]), _p(be.stats[1]), be.stats_bn_stride, _p(self.slots_t), len(self.slots),
+                  _p(self.cnt), _p(e.grads), e.Pp)
+        self._add("optim", None)
+        self._add("step", None)
+
+    def _head_args(self, train):
+        """The head launch (GAP, dense, softmax CE; v2: the final BN+ReLU first) and its HeadArgs.  Training: also the
+        backward of the dense layer and the final-BN reductions, under the static or per-member dynamic loss scale,
+        dense gradients into slabs.  Eval: statistics go to the sink, counts accumulate in ``ev_acc``.  v1 has no
+        final BN (gamma_off = beta_off = -1): its statistic pointers are placeholders."""
+        be, e, L = self.be, self.e, self.be.L
+        prog, cfg = L.prog, L.cfg
+        hwork = self._head_work() if train else self._work_member(target_items=HEAD_ITEMS)
+        ha = self._hold(HeadArgs())
+        ha.x, ha.labels, ha.work = _p(self.xs[-1]), _p(self.labels), _p(hwork)
+        ha.params, ha.p_mstride = _p(e.state), e.S
+        ha.gamma_off, ha.beta_off = (-1, -1) if self.v1 else self._bn(prog.final_bn)
+        ha.dw_off, ha.db_off = prog.dense_w_off, prog.dense_b_off
+        ha.g_mstride, ha.cnt = e.Pp, _p(self.cnt)
+        ha.hw, ha.C, ha.ncls, ha.train = L.final_hw, cfg.final_size, cfg.num_classes, int(train)
+        if train:
+            st = (be.stats, be.stats) if self.v1 else (be.st_f(prog.final_bn), be.st_b(prog.final_bn))
+            ha.st_f, ha.st_b, ha.grads = _p(st[0]), _p(st[1]), _p(e.grads)
+            ha.dfeat, ha.loss, ha.correct = _p(self.dfeat), _p(be.loss), _p(be.correct)
+            ha.loss_scale = be.loss_scale
+            ha.scale_tab = _p(e.lscale) if e.dynamic_loss_scale else None  # per-member dynamic scale
+            self._head_slab(ha, hwork)
+        else:
+            ha.st_f = _p(self.ev_sink if self.v1 else self._st_r(prog.final_bn))
+            ha.st_b, ha.correct, ha.loss = _p(self.ev_sink), _p(self.ev_acc[0]), _p(self.ev_acc[1])
+            ha.loss_scale = 1.0
+        self._add(ops.lib().dtf_head, ctypes.byref(ha), hwork.shape[0])
+        return ha
 
     def _build(self):
         if self.v1:
@@ -1292,36 +1290,14 @@ class _StepPlan:
         prog, cfg = L.prog, L.cfg
         lib = ops.lib()
         N = self.N
-        nslots = len(self.slots)
-        # 0. weights for this step
-        self._add(lib.dtf_weight_prep, _p(e.state), e.S, _p(be.conv_table_t), len(L.conv_table), _p(self.slots_t),
-                  nslots, _p(be.wf), _p(be.wd), L.wtot, *self._zero_args())
-        if self.src is not None:
-            self._add("augment", None)  # gather + pad/crop/flip + standardize + bf16 pack (data.hip)
-        else:
-            self._add(lib.dtf_prep_input, _p(self.x_in), _p(self.xin16), N * cfg.image_size * cfg.image_size, 3)
+        self._step_prologue()
         # ---------------- forward
         self._forward_v2()
         nblk = len(prog.blocks)
         # head (fwd + bwd of GAP/dense/CE + final-BN reductions)
         fb = prog.final_bn
         hw = L.final_hw
-        hwork = self._head_work()
-        ha = HeadArgs()
-        ha.x, ha.labels, ha.work = _p(self.xs[-1]), _p(self.labels), _p(hwork)
-        ha.params, ha.p_mstride = _p(e.state), e.S
-        ha.gamma_off, ha.beta_off = self._bn(fb)
-        ha.dw_off, ha.db_off = prog.dense_w_off, prog.dense_b_off
-        ha.grads, ha.g_mstride = _p(e.grads), e.Pp
-        ha.st_f, ha.st_b, ha.cnt = _p(be.st_f(fb)), _p(be.st_b(fb)), _p(self.cnt)
-        ha.dfeat, ha.loss, ha.correct = _p(self.dfeat), _p(be.loss), _p(be.correct)
-        ha.logits_out = None
-        ha.hw, ha.C, ha.ncls, ha.train = hw, cfg.final_size, cfg.num_classes, 1
-        ha.loss_scale = be.loss_scale
-        ha.scale_tab = _p(e.lscale) if e.dynamic_loss_scale else None  # per-member dynamic scale
-        self._head_slab(ha, hwork)
-        self._keep(ha)
-        self._add(lib.dtf_head, ctypes.byref(ha), hwork.shape[0])
+        ha = self._head_args(True)
         # (the moving-statistics update of the forward BNs runs at the end of the step, with the BN gradients)
         # ---------------- backward
         hwL = self.xs[-1].shape[1]
@@ -1389,15 +1365,7 @@ class _StepPlan:
         # stem wgrad (input = padded image, real channels 3)
         self._conv_wgrad(prog.stem, self.xin16, g_cur, mode_x=0, mode_dy=0, cin_real=cfg.in_channels)
         self._emit_deferred_wgrad()
-        # BN parameter gradients from the backward reductions
-        self._flush_slab()
-        self._flush_deferred()
-        self._add(lib.dtf_bn_step_end, _p(e.state), e.S, 3 * e.Pp, _p(be.bn_table_t), len(L.bn_table),
-                  _p(be.stats[0]), _p(be.stats[1]), be.stats_bn_stride, _p(self.slots_t), nslots, _p(self.cnt),
-                  _p(e.grads), e.Pp)
-        # optimizer over every member row (+ zero grads), step counters
-        self._add("optim", None)
-        self._add("step", None)
+        self._step_epilogue()
 
     def _forward_v2(self):
         """Stem + every pre-activation block (BN+ReLU prologues, BN-statistic epilogues, residual adds)."""
@@ -1448,60 +1416,19 @@ class _StepPlan:
         """Forward-only launch list of an eval chunk: bf16 weights of the evaluated members, moving statistics in
         accumulator form, input packing, the training forward kernels reading those statistics, and the head
         in inference mode (per-member correct count; optional logits)."""
-        be, e, L = self.be, self.e, self.be.L
-        prog, cfg = L.prog, L.cfg
-        lib = ops.lib()
-        nslots = len(self.slots)
-        self._add(lib.dtf_weight_prep, _p(e.state), e.S, _p(be.conv_table_t), len(L.conv_table), _p(self.slots_t),
-                  nslots, _p(be.wf), _p(be.wd), L.wtot, None, 0)
-        self._add(lib.dtf_bn_eval_stats, _p(e.state), e.S, 3 * e.Pp, _p(be.bn_table_t), len(L.bn_table),
-                  _p(self.ev_stats), be.stats_bn_stride, _p(self.slots_t), nslots, _p(self.cnt))
-        self._add(lib.dtf_prep_input, _p(self.x_in), _p(self.xin16), self.N * cfg.image_size * cfg.image_size, 3)
+        self._step_prologue()
         if self.v1:
             self._forward_v1()
         else:
             self._forward_v2()
-        hwork = self._work_member(target_items=HEAD_ITEMS)
-        ha = HeadArgs()
-        ha.x, ha.labels, ha.work = _p(self.xs[-1]), _p(self.labels), _p(hwork)
-        ha.params, ha.p_mstride = _p(e.state), e.S
-        if self.v1:
-            ha.gamma_off, ha.beta_off = -1, -1
-            ha.st_f = _p(self.ev_sink)
-        else:
-            ha.gamma_off, ha.beta_off = self._bn(prog.final_bn)
-            ha.st_f = _p(self._st_r(prog.final_bn))
-        ha.dw_off, ha.db_off = prog.dense_w_off, prog.dense_b_off
-        ha.grads, ha.g_mstride = None, e.Pp
-        ha.st_b, ha.cnt = _p(self.ev_sink), _p(self.cnt)
-        ha.dfeat, ha.correct, ha.loss = None, _p(self.ev_acc[0]), _p(self.ev_acc[1])
-        ha.logits_out = None
-        ha.hw, ha.C, ha.ncls, ha.train = L.final_hw, cfg.final_size, cfg.num_classes, 0
-        ha.loss_scale = 1.0
-        self._keep(ha)
-        self._head_args = ha
-        self._add(lib.dtf_head, ctypes.byref(ha), hwork.shape[0])
+        self.head_args = self._head_args(False)
 
     def want_logits(self):
         """Also write fp32 logits [N, ncls] of the next eval runs (numerics tests)."""
         if self.logits is None:
             self.logits = torch.zeros(self.N, self.be.L.cfg.num_classes, dtype=torch.float32, device=self.be.dev)
-            self._head_args.logits_out = _p(self.logits)
+            self.head_args.logits_out = _p(self.logits)
         return self.logits
-
-    def load_eval(self, x, y):
-        """The same eval images for every member: [m, H, W, 3] fp32 -> this plan's [members * m] input."""
-        m = x.shape[0]
-        k = len(self.slots)
-        assert all(n == m for n in self.sizes), "eval plans hold the same chunk for every member"
-        self.x_in.view(k, m, *self.x_in.shape[1:]).copy_(x.reshape(1, m, *self.x_in.shape[1:]).expand(k, -1, -1, -1,
-                                                                                                       -1))
-        self.labels.view(k, m).copy_(y.reshape(1, m).expand(k, -1))
-
-    def _zero_args(self):
-        """(buffer, n) zeroed by weight_prep: the statistic accumulators, losses and correct counts."""
-        be = self.be
-        return _p(be.zbuf), be.zbuf.numel()
 
     def _bn_bwd_apply(self, dz, x, add, out, bn):
         """out = BN-backward(dz, x) [+ add] (bn_bwd_apply_kernel)."""
@@ -1512,7 +1439,7 @@ class _StepPlan:
         ba.gamma_off = self._bn(bn)[0]
         ba.st_f, ba.st_b, ba.cnt = _p(be.st_f(bn)), _p(be.st_b(bn)), _p(self.cnt)
         ba.hw, ba.C, ba.nimg = x.shape[1] * x.shape[2], x.shape[3], self.N
-        self._keep(ba)
+        self._hold(ba)
         self._add(ops.lib().dtf_bn_bwd_apply, ctypes.byref(ba))
 
     def _bn_ew(self, fn, n_hw_c, bn1, h1, bn2=None, h2=None, add=None, out=None, d=None):
@@ -1531,12 +1458,12 @@ class _StepPlan:
         a.cap = self.sizes[0] if self.elastic else 0  # elastic: skip each member's capacity padding
         det_reduce = self.be.det and d is not None
         if det_reduce:  # deterministic build: per-image partial rows, added per member in image order
-            if getattr(self, "_det_rows", None) is None:
+            if self._det_rows is None:
                 self._det_rows = torch.zeros(self.N * 192, dtype=torch.float32, device=self.be.dev)
                 self._first_t = torch.tensor([self.first[s] for s in self.slots], dtype=torch.int32,
                                              device=self.be.dev)
             a.slab = _p(self._det_rows)
-        self._keep(a)
+        self._hold(a)
         self._add(fn, ctypes.byref(a))
         if det_reduce:
             self._add(ops.lib().dtf_bn_bwd_reduce_finish, ctypes.byref(a), _p(self._first_t), _p(self.slots_t),
@@ -1557,34 +1484,13 @@ class _StepPlan:
         prog, cfg = L.prog, L.cfg
         lib = ops.lib()
         N = self.N
-        nslots = len(self.slots)
         H = cfg.image_size
-        self._add(lib.dtf_weight_prep, _p(e.state), e.S, _p(be.conv_table_t), len(L.conv_table), _p(self.slots_t),
-                  nslots, _p(be.wf), _p(be.wd), L.wtot, *self._zero_args())
-        if self.src is not None:
-            self._add("augment", None)
-        else:
-            self._add(lib.dtf_prep_input, _p(self.x_in), _p(self.xin16), N * H * H, 3)
+        self._step_prologue()
         # ---------------- forward
         self._forward_v1()
         # head: GAP + dense + CE on the last block output (no final BN: gamma_off = -1)
         hw = L.final_hw
-        hwork = self._head_work()
-        ha_ = HeadArgs()
-        ha_.x, ha_.labels, ha_.work = _p(self.xs[-1]), _p(self.labels), _p(hwork)
-        ha_.params, ha_.p_mstride = _p(e.state), e.S
-        ha_.gamma_off, ha_.beta_off = -1, -1
-        ha_.dw_off, ha_.db_off = prog.dense_w_off, prog.dense_b_off
-        ha_.grads, ha_.g_mstride = _p(e.grads), e.Pp
-        ha_.st_f, ha_.st_b, ha_.cnt = _p(be.stats), _p(be.stats), _p(self.cnt)
-        ha_.dfeat, ha_.loss, ha_.correct = _p(self.dfeat), _p(be.loss), _p(be.correct)
-        ha_.logits_out = None
-        ha_.hw, ha_.C, ha_.ncls, ha_.train = hw, cfg.final_size, cfg.num_classes, 1
-        ha_.loss_scale = be.loss_scale
-        ha_.scale_tab = _p(e.lscale) if e.dynamic_loss_scale else None
-        self._head_slab(ha_, hwork)
-        self._keep(ha_)
-        self._add(lib.dtf_head, ctypes.byref(ha_), hwork.shape[0])
+        self._head_args(True)
         # (the moving-statistics update of the forward BNs runs at the end of the step, with the BN gradients)
         # ---------------- backward
         hwL = self.xs[-1].shape[1]
@@ -1631,19 +1537,13 @@ class _StepPlan:
         self._bn_ew(lib.dtf_bn_bwd_reduce, (H * H, cfg.num_filters), prog.stem_bn, self.h0, d=d)
         self._conv_wgrad(prog.stem, self.xin16, d, mode_x=0, mode_dy=2, dy_bn=prog.stem_bn, dy2=self.h0,
                          cin_real=cfg.in_channels)
-        self._flush_slab()
-        self._flush_deferred()
-        self._add(lib.dtf_bn_step_end, _p(e.state), e.S, 3 * e.Pp, _p(be.bn_table_t), len(L.bn_table),
-                  _p(be.stats[0]), _p(be.stats[1]), be.stats_bn_stride, _p(self.slots_t), nslots, _p(self.cnt),
-                  _p(e.grads), e.Pp)
-        self._add("optim", None)
-        self._add("step", None)
+        self._step_epilogue()
 
     # -------------------------------------------------------------------- execution
     def slot_index(self, slots):
         """Positions of ``slots`` in this plan's member list (device tensor, cached)."""
         key = tuple(slots)
-        cache = self.__dict__.setdefault("_slot_index", {})
+        cache = self._slot_index
         if key not in cache:
             pos = {s: i for i, s in enumerate(self.slots)}
             cache[key] = torch.tensor([pos[s] for s in slots], dtype=torch.long, device=self.be.dev)
@@ -1653,42 +1553,21 @@ class _StepPlan:
         """Stage the members' batches (``slots``: the members they belong to, default every plan member)."""
         slots = list(self.slots) if slots is None else [s for s in self.slots if s in set(slots)]
         # member regions start at self.first[slot] (packed for exact plans, capacity-strided for elastic ones)
-        if self.src is None and same_batches(self, batches):
-            return  # the staged copy is still current (same unmodified source storage)
-        if self.src is not None:
-            for s, b in zip(slots, batches):
-                n, off = len(b), self.first[s]
-                self.idx[off:off + n].copy_(b.idx, non_blocking=True)
-            if getattr(self, "_rng_stage", None) is None:
-                self._rng_stage = PinnedStager(2, torch.int32)
-            self._rng_stage.upload(self.rng, self.src.next_rng())
-            return
-        for s, (x, y) in zip(slots, batches):
-            n, off = x.shape[0], self.first[s]
-            self.x_in[off:off + n].copy_(x.reshape(n, *self.x_in.shape[1:]), non_blocking=True)
-            self.labels[off:off + n].copy_(y, non_blocking=True)
+        if self.src is None:
+            return super().load_batch(batches, slots)
+        for s, b in zip(slots, batches):
+            n, off = len(b), self.first[s]
+            self.idx[off:off + n].copy_(b.idx, non_blocking=True)
+        if self._rng_stage is None:
+            self._rng_stage = PinnedStager(2, torch.int32)
+        self._rng_stage.upload(self.rng, self.src.next_rng())
 
-    def _run_eager(self):
+    def _marker_augment(self, _):
+        """The "augment" marker of a plan fed index batches: on-device gather + augmentation inside the step graph;
+        crops keyed per member (its step counter + dataset row): placement-invariant (data.hip)."""
         e = self.e
-        for fn, args in self.launches:
-            if fn == "augment":
-                # crops keyed per member (its step counter + dataset row): placement-invariant (data.hip)
-                ops.augment_cifar(self.src.train_x, self.src.train_y, self.idx, self.rng, True, out16=self.xin16,
-                                  lab32=self.labels, member_keys=(self.img_slot, e.state, e.S, 3 * e.Pp + e.R))
-            elif fn == "optim":
-                run_optimizer(e, self.be, self.slots, self.slots_t, None)  # (+ dynamic loss scaling: hip_step.py)
-            elif fn == "step":
-                # step counters + per-member losses gathered inside the step (graph) so a replay leaves one copy
-                # for loss_view
-                advance_steps(e, self.slots_long, self.slots_t, self.be.loss, self.loss_sel, ring=self.ring)
-            else:
-                err = fn(*args, ops.stream())
-                if err != 0:
-                    raise RuntimeError("kernel launch %s failed with %d" % (getattr(fn, "__name__", fn), err))
-
-    def run_eval(self):
-        assert self.eval
-        self._run_eager()
+        ops.augment_cifar(self.src.train_x, self.src.train_y, self.idx, self.rng, True, out16=self.xin16,
+                          lab32=self.labels, member_keys=(self.img_slot, e.state, e.S, 3 * e.Pp + e.R))
 
     def run(self, train=True):
         run_captured(self)

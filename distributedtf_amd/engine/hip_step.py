@@ -1,11 +1,13 @@
 """What every HIP step backend shares: the driver around a family's kernels.
 
-A backend (``HipBackend``) owns the per-family device buffers and two bounded plan caches; a plan holds the buffers
-and the launch list of one batch composition, captured into a HIP graph on its first step (``run_captured``) and
-replayed afterwards.  The per-step host work -- optimizer hyper table (``upload_hyper``), small pinned uploads
-(``PinnedStager``), step counters and loss gather inside the graph (``advance_steps``, ``LossRing``) -- lives here
-too, as does the release of captured graphs before RCCL teardown (``release_graphs``).  The kernels, launch lists
-and ``infer`` of each family stay in its own ``hip_*`` module; this module imports none of them.
+A backend (``HipBackend``) owns the per-family device buffers, two bounded plan caches and the engine hooks every
+family answers alike (shadow refresh, ``infer`` through ``want_logits``); a plan (``HipPlan``) holds the member layout,
+the buffers and the launch list of one batch composition, stages its inputs (``load_batch``, ``load_eval``) and runs
+the list (``_run_eager``), captured into a HIP graph on its first step (``run_captured``) and replayed afterwards.
+The per-step host work -- optimizer hyper table (``upload_hyper``), small pinned uploads (``PinnedStager``), step
+counters and loss gather inside the graph (``advance_steps``, ``LossRing``) -- lives here too, as does the release of
+captured graphs before RCCL teardown (``release_graphs``).  The kernels, launch lists and family markers of each
+family stay in its own ``hip_*`` module; this module imports none of them.
 """
 
 from __future__ import annotations
@@ -228,11 +230,10 @@ def same_batches(plan, batches) -> bool:
     return False
 
 
-
 class HipBackend:
     """Driver of a population-batched HIP step backend: plan caches, the plain train step and chunked evaluation.
-    A family sets ``_plan_cls`` (constructed as ``_plan_cls(be, slots, sizes, eval_mode=False)``), allocates its
-    buffers -- ``loss`` and ``correct`` [capacity] among them -- and writes its own ``infer``."""
+    A family sets ``_plan_cls`` (constructed as ``_plan_cls(be, slots, sizes, eval_mode=False)``) and allocates its
+    buffers -- ``loss`` and ``correct`` [capacity] among them."""
 
     name = "hip"
     accepts_index_batches = False
@@ -254,6 +255,29 @@ class HipBackend:
         self._eval_plans = {}
         self.use_graph = (os.environ.get("DTF_HIP_GRAPH", "1") == "1" and os.environ.get("DTF_DEBUG", "0") != "1")
 
+    # ---- engine hooks
+    def shadow_weights(self):
+        return self.shadow
+
+    def on_params_changed(self, slots):
+        """Rows changed outside the optimizer (init, exploit import): refresh their low-precision shadow.  Families
+        without one read the fp32 master rows, or prepare their weights inside every step."""
+        slots = list(slots)
+        if self.shadow is not None and slots:
+            e = self.e
+            self._rows = ops.shadow_refresh(e.state, self.shadow, slots, e.Pp, e.P)
+
+    @torch.no_grad()
+    def infer(self, slot, x):
+        """Eval-mode logits of one member on the HIP forward kernels, for plans whose head writes them on request
+        (``want_logits``); the other families build theirs."""
+        p = self.eval_plan([slot], int(x.shape[0]))
+        logits = p.want_logits()
+        p.load_eval(x, torch.zeros(x.shape[0], dtype=torch.int32, device=x.device))
+        p.run_eval()
+        return logits.clone()
+
+    # ---- plans
     def plan(self, slots, sizes):
         key = (tuple(slots), tuple(sizes))
         p = self._plans.get(key)
@@ -319,18 +343,77 @@ class HipBackend:
 
 
 class HipPlan:
-    """What the plans that keep their step as a ``launches`` list share.  An entry is (launcher, args), run as
-    ``launcher(*args, stream)``, or one of the markers "zero" (args[0].zero_()), "optim" (gradient all-reduce of
-    data-parallel groups + the fused optimizer; it also writes the backend's ``shadow`` and unscales by its
-    ``loss_scale``) and "step" (step counters += 1, the backend's ``loss`` gathered into ``loss_sel``)."""
+    """What every step plan shares: the member layout of one batch composition, input staging, and the step as a
+    ``launches`` list.  An entry is (launcher, args), run as ``launcher(*args, stream)``, or one of the markers "zero"
+    (args[0].zero_()), "optim" (gradient all-reduce of data-parallel groups + the fused optimizer; it also writes the
+    backend's ``shadow`` and unscales by its ``loss_scale``) and "step" (step counters += 1, the backend's ``loss``
+    gathered into ``loss_sel``, or into the plan's ``ring``).  Any other string is a family's own marker, run as the
+    plan's ``_marker_<name>(*args)``.  A family's plan holds ``x_in`` [N, ...] fp32 and ``labels`` [N] int32."""
+
+    ring = None  # a LossRing where the plan hands out views of the per-step losses (_StepPlan)
+
+    def _init_members(self, be, slots, sizes, eval_mode=False, counts=None):
+        """The layout of ``sizes[i]`` images of member ``slots[i]``, packed in slot-list order: ``first`` (slot ->
+        first image), ``img_slot`` (image -> slot), ``cnt`` (slot -> images; ``counts`` where a member holds fewer
+        than its region, 0 for slots outside the plan), the slot lists, and an empty launch list."""
+        e, dev = be.e, be.dev
+        self.be, self.e, self.eval = be, e, bool(eval_mode)
+        self.slots, self.sizes, self.N = slots, sizes, sum(sizes)
+        img_slot, self.first = [], {}
+        for s, n in zip(slots, sizes):
+            self.first[s] = len(img_slot)
+            img_slot += [s] * n
+        self.img_slot = torch.tensor(img_slot, dtype=torch.int32, device=dev)
+        cnt = torch.zeros(e.capacity, dtype=torch.float32)
+        for s, n in zip(slots, sizes if counts is None else counts):
+            cnt[s] = float(n)
+        self.cnt = cnt.to(dev)
+        self.slots_t = torch.tensor(slots, dtype=torch.int32, device=dev)
+        self.slots_long = torch.tensor(slots, dtype=torch.long, device=dev)
+        self.loss_sel = torch.zeros(len(slots), dtype=be.loss.dtype, device=dev)
+        self.launches, self._keep, self.graph = [], [], None
 
     def _add(self, fn, *args):
         self.launches.append((fn, args))
 
     def _hold(self, obj):
+        """Keep ``obj`` (an argument struct, a work table) alive as long as the plan; returns it."""
         self._keep.append(obj)
         return obj
 
+    def _chunk_rows(self, s, n, chunk):
+        """Work rows (img0, nimg, 0, slot) over ``n`` images of member ``s`` in runs of ``chunk``."""
+        f = self.first[s]
+        return [[f + i, min(chunk, n - i), 0, s] for i in range(0, n, chunk)]
+
+    def _chunks(self, chunk):
+        """The int32 work table of every member's ``_chunk_rows``; ``chunk``: images per row, or a function of the
+        member's image count."""
+        rows = []
+        for s, n in zip(self.slots, self.sizes):
+            rows += self._chunk_rows(s, n, chunk(n) if callable(chunk) else chunk)
+        return torch.tensor(rows, dtype=torch.int32, device=self.be.dev)
+
+    # ---- input staging
+    def load_batch(self, batches, slots=None):
+        """Stage the members' (x, y) batches into their regions (``slots``: the members they belong to, default
+        every plan member), unless they are the unmodified storages staged last step."""
+        if same_batches(self, batches):
+            return
+        for s, (x, y) in zip(self.slots if slots is None else slots, batches):
+            n, off = x.shape[0], self.first[s]
+            self.x_in[off:off + n].copy_(x.reshape(n, *self.x_in.shape[1:]), non_blocking=True)
+            self.labels[off:off + n].copy_(y, non_blocking=True)
+
+    def load_eval(self, x, y):
+        """The same eval chunk for every member: [m, ...] fp32 -> this plan's [members * m] input."""
+        m, k = x.shape[0], len(self.slots)
+        assert all(n == m for n in self.sizes), "eval plans hold the same chunk for every member"
+        shp = tuple(self.x_in.shape[1:])
+        self.x_in.view(k, m, *shp).copy_(x.reshape(1, m, *shp).expand(k, *([-1] * (len(shp) + 1))))
+        self.labels.view(k, m).copy_(y.reshape(1, m).expand(k, -1))
+
+    # ---- execution
     def _run_eager(self):
         e, be = self.e, self.be
         st = ops.stream()
@@ -341,11 +424,17 @@ class HipPlan:
                 run_optimizer(e, be, self.slots, self.slots_t, be.shadow)
             elif fn == "step":
                 # step counters + per-member losses gathered inside the step (graph): a replay leaves one copy
-                advance_steps(e, self.slots_long, self.slots_t, be.loss, self.loss_sel)
+                advance_steps(e, self.slots_long, self.slots_t, be.loss, self.loss_sel, ring=self.ring)
+            elif isinstance(fn, str):
+                getattr(self, "_marker_" + fn)(*args)
             else:
                 err = fn(*args, st)
                 if err != 0:
-                    raise RuntimeError("kernel launch %s failed with %d" % (getattr(fn, "__name__", fn), err))
+                    raise RuntimeError("kernel launch %s failed with %d" % (ops.launcher_name(fn), err))
+
+    def run_eval(self):
+        assert self.eval
+        self._run_eager()
 
     def run(self):
         run_captured(self)

@@ -176,3 +176,88 @@ def test_import_layering_and_compatibility(fresh):
 def test_shutdown_releases_captured_graphs(fresh):
     assert not fresh["resnet_before_shutdown"]  # only the shared module was loaded
     assert fresh["graph_released"]
+
+
+# ---- HipPlan: the member layout, staging and launch-list runner every family's plan shares (no device needed)
+class _StubPlan(hip_step.HipPlan):
+    def __init__(self, slots, sizes, eval_mode=False, counts=None):
+        be = types.SimpleNamespace(e=types.SimpleNamespace(capacity=3), dev=torch.device("cpu"), loss=torch.zeros(3),
+                                   shadow=None)
+        self._init_members(be, slots, sizes, eval_mode, counts=counts)
+        self.x_in = torch.zeros(self.N, 2, 2)
+        self.labels = torch.zeros(self.N, dtype=torch.int32)
+        self.seen = []
+
+    def _marker_note(self, tag):
+        self.seen.append(("note", tag))
+
+
+def test_plan_member_layout():
+    p = _StubPlan([0, 2], [3, 2])
+    assert p.first == {0: 0, 2: 3} and p.N == 5
+    assert p.img_slot.tolist() == [0, 0, 0, 2, 2] and p.img_slot.dtype == torch.int32
+    assert p.cnt.tolist() == [3.0, 0.0, 2.0]  # 0 in the idle slot
+    assert p.slots_t.tolist() == [0, 2] and p.slots_long.dtype == torch.long and tuple(p.loss_sel.shape) == (2,)
+    assert p.launches == [] and p.graph is None and p.ring is None and not p.eval
+    # elastic form: the layout of the capacity sizes, the counts of the real ones
+    q = _StubPlan([0, 2], [3, 3], counts=[1, 2])
+    assert q.first == {0: 0, 2: 3} and q.N == 6 and q.cnt.tolist() == [1.0, 0.0, 2.0]
+
+
+def test_plan_member_chunks():
+    p = _StubPlan([0, 2], [3, 2])
+    assert p._chunks(2).tolist() == [[0, 2, 0, 0], [2, 1, 0, 0], [3, 2, 0, 2]]
+    assert p._chunks(1 << 30).tolist() == [[0, 3, 0, 0], [3, 2, 0, 2]]  # larger than any member: one row each
+    assert p._chunks(lambda n: n - 1).tolist() == [[0, 2, 0, 0], [2, 1, 0, 0], [3, 1, 0, 2], [4, 1, 0, 2]]
+    assert p._chunks(2).dtype == torch.int32 and p._chunk_rows(2, 0, 4) == []
+
+
+def test_plan_load_eval_replicates_the_chunk():
+    p = _StubPlan([0, 2], [2, 2], eval_mode=True)
+    x, y = torch.arange(8.0).reshape(2, 2, 2), torch.tensor([5, 7])
+    p.load_eval(x, y)
+    assert torch.equal(p.x_in[:2], x) and torch.equal(p.x_in[2:], x) and p.labels.tolist() == [5, 7, 5, 7]
+    with pytest.raises(AssertionError, match="same chunk"):
+        _StubPlan([0, 2], [2, 1], eval_mode=True).load_eval(x, y)
+
+
+def test_plan_load_batch_skips_an_unmodified_batch():
+    p = _StubPlan([0, 2], [3, 2])
+    batches = [(torch.full((3, 2, 2, 1), 1.0), torch.tensor([1, 1, 1])), (torch.full((2, 4), 2.0), torch.tensor([2, 2]))]
+    p.load_batch(batches)
+    assert p.x_in[:, 0, 0].tolist() == [1.0, 1.0, 1.0, 2.0, 2.0] and p.labels.tolist() == [1, 1, 1, 2, 2]
+    p.x_in.zero_()
+    p.load_batch(batches)  # the same storages, unmodified: nothing is staged again
+    assert float(p.x_in.abs().sum()) == 0.0
+    batches[1][0].add_(1.0)  # modified in place: staged again
+    p.load_batch(batches)
+    assert p.x_in[:, 0, 0].tolist() == [1.0, 1.0, 1.0, 3.0, 3.0]
+    # a subset of the members lands in their own regions
+    p.load_batch([(torch.full((2, 2, 2), 9.0), torch.tensor([4, 4]))], slots=[2])
+    assert p.x_in[:, 0, 0].tolist() == [1.0, 1.0, 1.0, 9.0, 9.0] and p.labels.tolist() == [1, 1, 1, 4, 4]
+
+
+def test_plan_runs_launchers_markers_and_names_a_failing_launcher(monkeypatch):
+    monkeypatch.setattr(hip_step.ops, "stream", lambda: "STREAM")
+    p = _StubPlan([0, 2], [3, 2], eval_mode=True)
+    buf = torch.ones(3)
+
+    def dtf_stub_ok(a, b, stream):
+        p.seen.append(("ok", a, b, stream))
+        return 0
+
+    def dtf_stub_fail(stream):
+        return 7
+
+    p._add("zero", buf)
+    p._add(dtf_stub_ok, 1, 2)
+    p._add("note", "family marker")
+    p.run_eval()
+    assert p.seen == [("ok", 1, 2, "STREAM"), ("note", "family marker")] and buf.tolist() == [0.0, 0.0, 0.0]
+    p._add(dtf_stub_fail)
+    p._add("note", "not reached")
+    with pytest.raises(RuntimeError, match="dtf_stub_fail failed with 7"):
+        p.run_eval()
+    assert p.seen[-1] == ("note", "family marker")
+    with pytest.raises(AssertionError):
+        _StubPlan([0], [1]).run_eval()  # a training plan is not an eval plan

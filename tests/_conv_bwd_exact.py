@@ -1,0 +1,596 @@
+"""Constructions for the exact tests of the deferred CIFAR backward kernels of ops/csrc/conv.hip: the dgrad role
+``dtf_conv_bwd_dg`` (13 instantiations), the deferred weight-gradient launch ``dtf_conv_wgrad_all`` with its dW slabs,
+and the slab reductions ``dtf_slab_reduce_all`` / ``dtf_dw_slab_reduce``.  Operands, float64 references, exactness
+conditions and buffer layouts, all without a device; the population layout, the work lists, the guarded buffers and
+the BN+ReLU snap construction are those of tests/_conv_exact.py.  Used by tests/test_gpu_conv_bwd_dg.py,
+tests/test_gpu_conv_wgrad_deferred.py and, for the conditions themselves, tests/test_conv_bwd_exact_constructions.py.
+(``dtf_conv_bwd_fused``, ``dtf_conv_dgrad``, ``dtf_conv_wgrad`` and ``dtf_conv_trans_multi`` are not covered; the
+cases here are keyed by (C, mode, epi, rows) so that further roles can be added beside them.)
+
+Geometry.  The kernels' compile-time ones: H = W = 512 / C at C = 16, 32, 64, bands of 8 rows (4: half-image bands of
+the dgrad role at C = 64).
+
+dgrad role.  dx[r][c][ci] = sum over (ky, kx, co) of W[ci][ky][kx][co] T(dy)[r + 1 - ky][c + 1 - kx][co] (IHWO weights,
+zero outside the image), y = BN_x(x) > 0 ? dx [+ res] : 0 rounded to the activation type, and the launch adds
+sum(y) and sum(y xhat(x)) per member and channel to one statistics replica per workgroup.  Weights are integers
+(+-1, +-2 on integer dY; +-1 on the 0.5 grid of a transformed dY), about 8 non-zero per input channel, so every
+product and every partial sum is a multiple of u (1 or 0.5); with (``check_dg``, asserted on the reference alone)
+
+* sum of |terms| < 2^24 u per dx element and |dx + res| <= 256 u,
+* per member and channel sum |y| < 2^24 u, the seed of the accumulator rows included,
+
+y and the sum(y) row are the float64 words in any order of summation.  The mask is the forward snap construction of
+_conv_exact (every pre-activation within 2^-12 of a point k + 0.5, |k + 0.5| >= 0.5, inside a quarter of the bf16
+spacing together with the kernel's fp32 error): no mask decision is near its edge.  The sum(y xhat) row goes through
+rsqrtf and is compared with float64 against 4 x the scaled deviation of a float32 evaluation of the same formula.
+
+Transformed dY (MODE_DY 2: BN-backward(dz, h); 3: the same + x3), the backward snap construction.  ``bn_bwd_coef``
+evaluates in fp32 mean = s / n, inv = rsqrtf(max(q / n - mean^2, 0) + 1e-5), scale = gamma inv, mdz = sdz / n, mdzx =
+sdzx / n, A = scale, B = -scale inv mdzx, C = -scale mdz + scale inv mean mdzx, and stages A dz + B h + C [+ x3]
+= scale [(dz - mdz) - inv mdzx (h - mean)] [+ x3].  Per (member, channel) the test picks inv in {0.5, 1, 2}, mean in
+{0, +-1, +-2, 0.5}, gamma in {+-0.5, +-1, +-2}, t = inv mdzx in {0, +-0.5, +-1} and mdz in {0, +-0.5, +-1} (mdz and mdzx
+dyadic), writes (s, q) and (sdz, sdzx) as fp32 replica words split unevenly with one share negative, and builds
+
+    dz = mdz + odd / (2 |scale|),  odd in {-5 .. 5},      h = mean + m max(1, 1 / |scale|) / t,  m in {-2 .. 2}
+
+so that scale (dz - mdz) is an odd multiple of 0.5 and scale t (h - mean) an integer: the staged value is ideally
+k + 0.5, |k + 0.5| <= 10.5 (13.5 with the integer x3 in [-3, 3]).  The reference evaluates the transform in float64
+FROM THE SAME fp32 words and asserts per staged element v, with snap(v) the nearest multiple of 0.5,
+
+* |v - snap(v)| <= 2^-12 max(|v|, 1), snap(v) an odd multiple of 0.5, and
+* |v - snap(v)| + E < (spacing of bf16 at snap(v)) / 4 (fp16 is finer there), where E bounds the kernel's own fp32
+  error.  A, B and C all carry the kernel's scale as a factor, so with the relative errors e_inv = K (NREP + 3) 2^-24
+  A_f + 2^-21 of inv and scale (K = (q / n) / (var + eps) <= 17 the amplification of the variance, A_f = sum |shares|
+  / |sum| that of the forward replica sums, as in _conv_exact), e_s = (NREP + 3) 2^-24 A_f + 2^-23 of mean and e_z,
+  e_x = (NREP + 3) 2^-24 A_b + 2^-23 of mdz and mdzx:
+  E = |v - x3| e_inv + |scale inv mdzx (h - mean)| (e_inv + e_x) + |scale inv mdzx mean| e_s + |scale mdz| e_z
+      + (|A dz| + |B h| + |C| + |scale mdz| + |scale inv mean mdzx| + |v|) 2^-21,
+  the last term for the roundings of the products and sums themselves (at most four per term).
+
+The conv then uses snap(v) as dY, and ``xout`` must hold snap(v) over the band interior.  One channel per member has
+gamma = 0 and q / n < mean^2 - 1e-5: with the ``fmaxf(..., 0)`` clamp A = B = C = 0 and the staged value is exactly 0
+(x3 in MODE 3), without it NaN.
+
+Deferred wgrad.  dW[co][ky][kx][ci] = sum over pixels of T(dy)[p][co] relu(BN_x(x))[p + (ky - 1, kx - 1)][ci]: dY an
+integer in [-3, 3] (mode 0) or the snapped transform above (mode 2), x the forward snap construction, so every product
+is a multiple of u = 0.5 or 0.25 and (``check_wg``) sum of |terms| < 2^24 u per dW element, the integer seed of the
+gradient row included: per-workgroup slabs, their reduction and the atomic flush give the float64 words in any order.
+A job's work list has the cuts of the hand-listed cases, but grouped by member (slot 2 first): the reduce table
+(first wg, n wgs, -, slot) needs a member's slabs contiguous, and two rows of one slot would race on the gradient row.
+The jobs of a launch are interleaved by its ``map`` instead.
+
+Slab layout.  A slab is [j][m][t][r] (NJ = ceil(NTN / 4) x MT = C / 16 x 256 threads x 4): tile nt = t / 64 + 4 j of
+the NTN = 9 C / 16 (tap, ci) tiles, (tap, ci) = (16 nt / C, 16 nt % C + t % 16), co = 16 m + 4 (t % 64 / 16) + r; tiles
+nt >= NTN (C = 16 and C = 32 have them) are duplicates that a reduction must skip (``slab_map``)."""
+import functools
+
+import torch
+import torch.nn.functional as F
+
+import _conv_exact as kx
+from _conv_exact import (BN_EPS, CAP, EXACT, LISTED, PRE, UNIFORM, assert_tiling, guarded, guards_intact,  # noqa: F401
+                         hints, hpick, listed_items, live, poison_work, ranges, uniform_geo, work_item_at)
+
+NAN = float("nan")
+IN_GAMMA, EP_GAMMA, EP_BETA = 37, 131, 211  # params row (kx.P_MSTRIDE wide): dY BN gamma, mask BN gamma / beta
+G_OFF, G_GAP = 24, 40  # gradient row: words before the first layer's block and after every block
+FACTOR_RSQRT = 4.0  # tests/_resnet_aux_exact.py: allowed multiple of the float32 yardstick's deviation
+WIDTHS = (16, 32, 64)
+
+
+class Case:
+    pass
+
+
+def slab_elems(c):
+    return ((9 * c // 16 + 3) // 4) * (c // 16) * 4 * 256
+
+
+def tile_elems(c, rows, wpitch):
+    """TSZ of conv_bwd_body: one [rows + 2][wpitch][cpad] tile, rounded up to 64 elements."""
+    cpad = {16: 16, 32: 48, 64: 80}[c]
+    return ((rows + 2) * wpitch * cpad + 8 + 63) // 64 * 64
+
+
+def lds_dg(c, rows, wpitch):
+    return 2304 + 2 * tile_elems(c, rows, wpitch) * 2
+
+
+def lds_wg(c, wpitch):
+    return 2304 + 4 * tile_elems(c, 8, wpitch) * 2
+
+
+@functools.lru_cache(maxsize=None)
+def slab_map(c):
+    """[slab_elems(c)][3] int64: (co, tap, ci) of every slab element, (-1, -1, -1) for the duplicate tiles."""
+    mt, ntn = c // 16, 9 * c // 16
+    nj = (ntn + 3) // 4
+    out = []
+    for j in range(nj):
+        for m in range(mt):
+            for t in range(256):
+                wave, lane = t // 64, t % 64
+                nt = wave + 4 * j
+                for r in range(4):
+                    if nt >= ntn:
+                        out.append((-1, -1, -1))
+                    else:
+                        out.append((16 * m + 4 * (lane // 16) + r, (16 * nt) // c, (16 * nt) % c + lane % 16))
+    return torch.tensor(out, dtype=torch.int64)
+
+
+def slab_index(c):
+    """(valid [E] bool, flat index co * 9 * C + tap * C + ci [E]) of a slab's elements."""
+    m = slab_map(c)
+    valid = m[:, 0] >= 0
+    return valid, (m[:, 0] * 9 + m[:, 1]) * c + m[:, 2]
+
+
+# ------------------------------------------------------------------------------------------------ operands
+def _geo(c, cc, rows, uniform, nrep):
+    c.C = c.cin = c.cout = cc
+    c.k, c.H, c.hi, c.wi, c.rows, c.nrep, c.uniform = 3, 512 // cc, 512 // cc, 512 // cc, rows, nrep, uniform
+    c.bands = c.H // rows
+    c.slots, c.sizes = UNIFORM if uniform else LISTED
+    c.idle = [s for s in range(CAP) if s not in c.slots][0]
+    c.n_img = sum(c.sizes)
+
+
+def _work(c, grouped):
+    if c.uniform:
+        per = c.sizes[0] * c.bands
+        c.u = uniform_geo(per, kx.uniform_chunk(per))
+        c.items = [work_item_at(b, *c.u) for b in range(c.u[0] * len(c.slots))]
+    else:
+        c.u = (0, 0, 0)
+        c.items = listed_items(c.slots, c.sizes, c.bands)
+        if grouped:
+            c.items = sorted(c.items, key=lambda it: (-it[3], it[0]))
+
+
+def red_table(items):
+    """(first wg, n wgs, 0, slot) per run of one slot in a work list (hip_resnet._slab_table)."""
+    rows = []
+    for i, it in enumerate(items):
+        if rows and rows[-1][3] == it[3] and rows[-1][0] + rows[-1][1] == i:
+            rows[-1][1] += 1
+        else:
+            rows.append([i, 1, 0, it[3]])
+    return rows
+
+
+def _mask_bn(c, seed):
+    """The BN of the layer input x (dgrad: the mask; wgrad: the BN+ReLU operand): kx._bn_input on the case's geometry."""
+    e = Case()
+    e.cin, e.hi, e.wi, e.slots, e.sizes, e.nrep = c.C, c.H, c.H, c.slots, c.sizes, c.nrep
+    kx._bn_input(e, seed)
+    e.mode, e.y, e.w = 1, None, None
+    return e
+
+
+def _shares(nrep, seed):
+    sh = 1.0 + (kx._hash((CAP, nrep, 2, 64), seed) % 7).double()
+    sh[:, 1] = -0.25 * sh[:, 1]
+    return sh / sh.sum(1, keepdim=True)
+
+
+def _amp(w):
+    """sum |shares| / |sum| per (row, channel) of replica words [nrep][2][C] (a zero sum has zero shares)."""
+    s = w.sum(0)
+    return torch.where(s == 0, torch.zeros_like(s), w.abs().sum(0) / s.abs().clamp(min=1e-30))
+
+
+def _bn_bwd_input(c, seed, x3):
+    """The MODE_DY 2 / 3 operands of case c (see the module docstring): c.dz, c.h, c.x3, c.dgamma, c.st_f, c.st_b and
+    the float64 staged values c.dv with their snap c.dy and error bound c.derr."""
+    cc, hh, n_img, nrep = c.C, c.H, c.n_img, c.nrep
+    inv = hpick((CAP, cc), [0.5, 1.0, 2.0], seed + 20)
+    mean = hpick((CAP, cc), [0.0, 1.0, -1.0, 2.0, -2.0, 0.5], seed + 21)
+    gamma = hpick((CAP, cc), [0.5, -0.5, 1.0, -1.0, 2.0, -2.0], seed + 22)
+    t = hpick((CAP, cc), [-1.0, -0.5, 0.0, 0.5, 1.0], seed + 23)
+    mdz = hpick((CAP, cc), [0.0, 0.5, -0.5, 1.0, -1.0], seed + 24)
+    qn = 1.0 / inv ** 2 - BN_EPS + mean ** 2
+    c.dclamp = {}
+    for s in range(CAP):
+        ch = (9 + 5 * s) % cc
+        c.dclamp[s] = ch
+        gamma[s, ch], mean[s, ch], qn[s, ch], t[s, ch], mdz[s, ch] = 0.0, 2.0, 4.0 - 1e-3, 1.0, 1.0
+    sc = gamma * inv
+    se = torch.where(sc == 0, torch.ones_like(sc), sc.abs())
+    tz = torch.where(t == 0, torch.ones_like(t), t)
+    shape = (n_img, hh, hh, cc)
+    odd = (2 * (kx._hash(shape, seed + 25) % 6) - 5).double()
+    mm = (kx._hash(shape, seed + 26) % 5).double() - 2
+    c.dz, c.h = torch.empty(shape, dtype=torch.float64), torch.empty(shape, dtype=torch.float64)
+    for s, f, e in ranges(c.slots, c.sizes):
+        c.dz[f:e] = mdz[s] + odd[f:e] * 0.5 / se[s]
+        c.h[f:e] = mean[s] + mm[f:e] * (1.0 / se[s]).clamp(min=1.0) / tz[s]
+    c.x3 = hints(shape, -3, 3, seed + 27) if x3 else None
+    tot_f, tot_b = torch.zeros(CAP, 2, 64, dtype=torch.float64), torch.zeros(CAP, 2, 64, dtype=torch.float64)
+    for s, f, e in ranges(c.slots, c.sizes):
+        n = (e - f) * hh * hh
+        tot_f[s, 0, :cc], tot_f[s, 1, :cc] = (mean[s] * n).float().double(), (qn[s] * n).float().double()
+        tot_b[s, 0, :cc], tot_b[s, 1, :cc] = mdz[s] * n, t[s] / inv[s] * n
+    c.st_f = (_shares(nrep, seed + 28) * tot_f[:, None]).float()
+    c.st_b = (_shares(nrep, seed + 29) * tot_b[:, None]).float()
+    c.st_f[c.idle] = c.st_b[c.idle] = NAN
+    gamma[c.idle] = NAN
+    c.dgamma, c.d_t, c.d_mdz = gamma, t, mdz
+    c.dv, c.derr = torch.empty(shape, dtype=torch.float64), torch.empty(shape, dtype=torch.float64)
+    eps = float(torch.tensor(BN_EPS, dtype=torch.float32))
+    for s, f, e in ranges(c.slots, c.sizes):
+        n = (e - f) * hh * hh
+        wf, wb = c.st_f[s].double()[:, :, :cc], c.st_b[s].double()[:, :, :cc]
+        mu, q = wf[:, 0].sum(0) / n, wf[:, 1].sum(0)
+        var = (q / n - mu * mu).clamp(min=0.0)
+        iv = 1.0 / torch.sqrt(var + eps)
+        scl = gamma[s].float().double() * iv
+        z, zx = wb[:, 0].sum(0) / n, wb[:, 1].sum(0) / n
+        a, b, k0 = scl, -scl * iv * zx, -scl * z + scl * iv * mu * zx
+        dz, h = c.dz[f:e], c.h[f:e]
+        v0 = a * dz + b * h + k0
+        c.dv[f:e] = v0 + (c.x3[f:e] if x3 else 0.0)
+        af, ab = _amp(wf), _amp(wb)
+        rep = (nrep + 3) * 2.0 ** -24
+        e_inv = (q / n) / (var + BN_EPS) * rep * af.max(0).values + 2.0 ** -21
+        e_s, e_z, e_x = rep * af[0] + 2.0 ** -23, rep * ab[0] + 2.0 ** -23, rep * ab[1] + 2.0 ** -23
+        c.derr[f:e] = (v0.abs() * e_inv + (scl * iv * zx * (h - mu)).abs() * (e_inv + e_x)
+                       + (scl * iv * zx * mu).abs() * e_s + (scl * z).abs() * e_z
+                       + ((a * dz).abs() + (b * h).abs() + k0.abs() + (scl * z).abs() + (scl * iv * mu * zx).abs()
+                          + c.dv[f:e].abs()) * 2.0 ** -21)
+        c.derr[f:e][..., gamma[s] == 0] = 0.0  # scale = 0 * inv exactly: A = B = C = 0
+    c.dy = torch.round(2 * c.dv) / 2
+
+
+def _plain_dy(c, seed):
+    c.dy = hints((c.n_img, c.H, c.H, c.C), -3, 3, seed + 25)
+    c.dz, c.h, c.x3 = c.dy, None, None
+    c.dgamma = torch.full((CAP, c.C), NAN, dtype=torch.float64)
+    c.st_f = c.st_b = torch.full((CAP, c.nrep, 2, 64), NAN)
+
+
+def check_dy(c):
+    """The representability and snap conditions of a case's dY operands."""
+    for t in (c.dz, c.h, c.x3):
+        if t is not None:
+            for dt in (torch.bfloat16, torch.float16):
+                assert torch.equal(t.to(dt).double(), t), "operand not representable"
+    assert bool((c.dz.flip(1) != c.dz).any()) and bool((c.dz.flip(2) != c.dz).any())
+    if c.mode == 0:
+        assert bool((c.dy == c.dy.round()).all()) and c.dy.abs().max() <= 3
+        return
+    v, sn = c.dv, c.dy
+    assert bool(((v - sn).abs() <= 2.0 ** -12 * v.abs().clamp(min=1.0)).all()), float((v - sn).abs().max())
+    assert sn.abs().max() <= 13.5
+    nz = sn != 0
+    quarter = 2.0 ** (torch.floor(torch.log2(sn.abs().clamp(min=0.5))) - 7 - 2)
+    assert bool((((v - sn).abs() + c.derr < quarter) | ~nz).all()), float(((v - sn).abs() + c.derr)[nz].max())
+    assert bool((v[~nz] == 0).all()) and bool((c.derr[~nz] == 0).all())
+    for s, f, e in ranges(c.slots, c.sizes):
+        ch = c.dclamp[s]
+        keep = torch.ones(c.C, dtype=torch.bool)
+        keep[ch] = False
+        assert bool(((2 * sn[f:e][..., keep]) % 2 == 1).all()), "a staged value off the k + 0.5 grid"
+        assert c.dgamma[s, ch] == 0 and torch.equal(v[f:e, :, :, ch], c.x3[f:e, :, :, ch] if c.mode == 3 else
+                                                    torch.zeros_like(v[f:e, :, :, ch]))
+        n = (e - f) * c.H * c.H
+        wf, wb = c.st_f[s].double()[:, :, :c.C], c.st_b[s].double()[:, :, :c.C]
+        assert float(wf[:, 1, ch].sum() / n - (wf[:, 0, ch].sum() / n) ** 2) < -BN_EPS  # NaN without the clamp
+        assert bool((c.dgamma[s] < 0).any()) and bool((c.d_t[s] == 0).any()) and bool((c.d_t[s] < 0).any())
+        for w in (wf, wb):  # uneven replica shares, one negative (a zero sum has zero shares)
+            live_ = w.sum(0) != 0
+            assert bool(((w < 0).any(0) | ~live_).all()) and bool(((w.max(0).values != w.min(0).values) | ~live_).all())
+    assert bool(torch.isnan(c.st_f[c.idle]).all()) and bool(torch.isnan(c.st_b[c.idle]).all())
+    assert bool(torch.isnan(c.dgamma[c.idle]).all())
+
+
+def check_mask_bn(c):
+    """The forward snap conditions of kx.check_case on the BN of the layer input."""
+    e = c.ep
+    v, sn = e.v, e.snap
+    for dt in (torch.bfloat16, torch.float16):
+        assert torch.equal(e.x.to(dt).double(), e.x)
+    assert bool(((v - sn).abs() <= 2.0 ** -12 * v.abs().clamp(min=1.0)).all())
+    assert sn.abs().min() >= 0.5 and sn.abs().max() <= 63.5
+    quarter = 2.0 ** (torch.floor(torch.log2(sn.abs())) - 7 - 2)
+    assert bool(((v - sn).abs() + e.err < quarter).all())
+    assert bool((sn > 0).any()) and bool((sn < 0).any())
+    for s, f, e_ in ranges(c.slots, c.sizes):
+        ch = e.clamp_ch[s]
+        assert e.gamma[s, ch] == 0 and bool((v[f:e_, :, :, ch] == 1.5).all())
+        w = e.st_in[s].double()
+        n = (e_ - f) * c.H * c.H
+        assert float(w[:, 1, ch].sum() / n - (w[:, 0, ch].sum() / n) ** 2) < -BN_EPS
+    assert bool(torch.isnan(e.st_in[c.idle]).all()) and bool(torch.isnan(e.gamma[c.idle]).all())
+    assert bool(torch.isnan(e.cnt[c.idle]))
+
+
+def check_work(c, grouped):
+    assert_tiling(c.items, c.slots, c.sizes, c.bands)
+    if c.uniform:
+        ui, uc, up = c.u
+        assert up % uc != 0 and ui == -(-up // uc) and c.slots == tuple(range(len(c.slots))) and len(set(c.sizes)) == 1
+    else:
+        cov = kx.items_coverage(c.items, c.bands)
+        assert all(cov[k] for k in kx.ITEMS_NEED), cov
+        if grouped:
+            assert len(red_table(c.items)) == len(c.slots)
+        else:
+            assert len(red_table(c.items)) > len(c.slots), "the members' items are interleaved"
+
+
+def param_rows(c):
+    rows = torch.full((CAP, kx.P_MSTRIDE), NAN, dtype=torch.float64)
+    rows[:, IN_GAMMA:IN_GAMMA + c.C] = c.dgamma
+    rows[:, EP_GAMMA:EP_GAMMA + c.C] = c.ep.gamma
+    rows[:, EP_BETA:EP_BETA + c.C] = c.ep.beta
+    return rows
+
+
+# ------------------------------------------------------------------------------------------- the dgrad role
+# every instantiation of dtf_conv_bwd_dg: (C, MODE_DY, EPI, rows)
+DG_CASES = ([(cc, 0, 0, 8) for cc in WIDTHS] + [(cc, 3, 0, 8) for cc in WIDTHS] + [(cc, 2, 0, 8) for cc in WIDTHS]
+            + [(16, 2, 1, 8)] + [(64, m, 0, 4) for m in (0, 2, 3)])
+DG_NULL_XOUT = [(32, 2, 0, 8), (16, 3, 0, 8)]  # one case per MODE_DY >= 2 launched without xout
+DG_REJECTS = [(32, 0, 0, 4), (16, 0, 2, 8), (48, 0, 0, 8)]  # rows = 4 with C = 32, epi = 2, C = 48
+DG_UNTESTED = []  # instantiations whose construction cannot meet its conditions (none)
+
+
+@functools.lru_cache(maxsize=None)
+def dg_case(cc, mode, epi, rows, uniform=False, nrep=8):
+    c = Case()
+    _geo(c, cc, rows, uniform, nrep)
+    c.mode, c.epi = mode, epi
+    seed = (cc * 131 + mode * 17 + epi * 5 + rows) * 1009 + uniform * 7919 + 424247
+    c.ep = _mask_bn(c, seed)
+    if mode == 0:
+        _plain_dy(c, seed)
+    else:
+        _bn_bwd_input(c, seed, mode == 3)
+    c.unit = 1.0 if mode == 0 else 0.5
+    c.w = kx._weights(c, seed, 12 if mode == 0 else 10)  # IHWO: [CAP][Ci][3][3][Co]
+    c.res = hints((c.n_img, c.H, c.H, cc), -8, 8, seed + 3) if epi & 1 else None
+    shape = (c.n_img, c.H, c.H, cc)
+    c.y, c.absy = torch.empty(shape, dtype=torch.float64), torch.empty(shape, dtype=torch.float64)
+    c.st = torch.zeros(CAP, 64, dtype=torch.float64)
+    c.st_abs = torch.zeros(CAP, 64, dtype=torch.float64)
+    for sl, f, e in ranges(c.slots, c.sizes):
+        wt = c.w[sl].permute(3, 0, 1, 2).contiguous()  # conv_transpose2d weight [Co][Ci][ky][kx]
+        dyn = c.dy[f:e].permute(0, 3, 1, 2).contiguous()
+        dx = F.conv_transpose2d(dyn, wt, padding=1).permute(0, 2, 3, 1)
+        ab = F.conv_transpose2d(dyn.abs(), wt.abs(), padding=1).permute(0, 2, 3, 1)
+        if epi & 1:
+            dx, ab = dx + c.res[f:e], ab + c.res[f:e].abs()
+        c.absy[f:e] = ab
+        c.y[f:e] = torch.where(c.ep.snap[f:e] > 0, dx, torch.zeros_like(dx))
+        c.st[sl, :cc] = c.y[f:e].sum((0, 1, 2))
+        c.st_abs[sl, :cc] = c.y[f:e].abs().sum((0, 1, 2))
+    c.w[c.idle] = NAN
+    c.st_seed = 1.0 + hints((CAP, nrep, 2, 64), 0, 4, seed + 4)
+    _work(c, grouped=False)
+    return c
+
+
+def check_dg(c):
+    """Every exactness and snap condition of a dgrad case, on the operands and the reference alone."""
+    u = c.unit
+    check_dy(c)
+    check_mask_bn(c)
+    act = list(c.slots)
+    for t in (c.w[act], c.y, c.dy) + ((c.res,) if c.epi & 1 else ()):
+        for dt in (torch.bfloat16, torch.float16):
+            assert torch.equal(t.to(dt).double(), t), "operand not representable"
+    assert bool((c.w[act] == c.w[act].round()).all()) and bool((c.y / u == (c.y / u).round()).all())
+    assert c.absy.max() < EXACT * u and c.absy.max() <= 256 * u, float(c.absy.max())
+    seed_abs = c.st_seed.abs().sum(1).max()
+    assert c.st_abs.max() + seed_abs < EXACT * u
+    assert bool((c.st_seed != 0).all()) and bool((c.st_seed == c.st_seed.round()).all())
+    for sl in c.slots:
+        assert bool(((c.w[sl] != 0).sum((0, 1, 2)) > 0).all()) and bool(((c.w[sl] != 0).sum((1, 2, 3)) > 0).all())
+        assert bool(((c.w[sl] != 0).sum((0, 3)) > 0).all()), "a tap without a weight"
+    assert not torch.equal(c.w[c.slots[0]], c.w[c.slots[1]]) and bool(torch.isnan(c.w[c.idle]).all())
+    assert bool((c.y != 0).any()) and bool(((c.ep.snap < 0) & (c.absy > 0)).any()), "the mask removes something"
+    check_work(c, grouped=False)
+
+
+def dg_replica_rows(c):
+    """[CAP][nrep][64]: the sum(dz) row of every statistics replica after the launch -- workgroup b adds the sum over
+    its own iterations to replica b % nrep of its member (exact: every partial sum is a small multiple of u)."""
+    exp = c.st_seed[:, :, 0].clone()
+    for b, (it0, nit, _, s) in enumerate(c.items):
+        for it in range(it0, it0 + nit):
+            img, r0 = it // c.bands, (it % c.bands) * c.rows
+            exp[s, b % c.nrep, :c.C] += c.y[img, r0:r0 + c.rows].sum((0, 1))
+    return exp
+
+
+def dg_xhat(c, dtype):
+    """(value, magnitude) [CAP][64] at ``dtype`` of the sum(y xhat) row, all replicas summed and their seed included:
+    the kernel's formula xhat = x inv + (-mean inv) from the fp32 words of the mask BN's statistics, the replicas
+    added in order, the images one at a time."""
+    cc = c.C
+    val = c.st_seed[:, :, 1].sum(1).to(dtype)
+    mag = c.st_seed[:, :, 1].abs().sum(1).to(dtype)
+    eps = torch.tensor(BN_EPS, dtype=torch.float32).to(dtype)
+    for s, f, e in ranges(c.slots, c.sizes):
+        n = float((e - f) * c.H * c.H)
+        w = c.ep.st_in[s].to(dtype)
+        sm, q = torch.zeros(cc, dtype=dtype), torch.zeros(cc, dtype=dtype)
+        for r in range(c.nrep):
+            sm, q = sm + w[r, 0, :cc], q + w[r, 1, :cc]
+        mean = sm / n
+        inv = 1.0 / torch.sqrt((q / n - mean * mean).clamp(min=0.0) + eps)
+        y, x = c.y[f:e].to(dtype), c.ep.x[f:e].to(dtype)
+        t = (y * (x * inv + (-mean * inv))).sum((1, 2))
+        tm = ((y * x * inv).abs() + (y * mean * inv).abs()).sum((1, 2))
+        for i in range(e - f):
+            val[s, :cc] += t[i]
+            mag[s, :cc] += tm[i]
+    return val, mag
+
+
+# --------------------------------------------------------------------------------------- the deferred wgrad
+WG_SETS = {0: [(64, 0), (32, 2), (64, 2), (32, 0)], 1: [(16, 2), (16, 0)]}  # cset -> jobs (C, dY mode) of one launch
+
+
+@functools.lru_cache(maxsize=None)
+def wg_job(cc, mode, uniform=False, nrep=8):
+    c = Case()
+    _geo(c, cc, 8, uniform, nrep)
+    c.mode, c.epi = mode, 0
+    seed = (cc * 137 + mode * 19) * 1013 + uniform * 7919 + 990001
+    c.ep = _mask_bn(c, seed)
+    if mode == 0:
+        _plain_dy(c, seed)
+    else:
+        _bn_bwd_input(c, seed, False)
+    c.unit = 0.5 if mode == 0 else 0.25
+    hh = c.H
+    c.dw = torch.zeros(CAP, cc, 3, 3, cc, dtype=torch.float64)  # [slot][co][ky][kx][ci]
+    c.absdw = torch.zeros_like(c.dw)
+    xp = F.pad(c.ep.xin, (0, 0, 1, 1, 1, 1))
+    for sl, f, e in ranges(c.slots, c.sizes):
+        for ky in range(3):
+            for kx_ in range(3):
+                xs = xp[f:e, ky:ky + hh, kx_:kx_ + hh]
+                c.dw[sl, :, ky, kx_] = torch.einsum("nhwo,nhwi->oi", c.dy[f:e], xs)
+                c.absdw[sl, :, ky, kx_] = torch.einsum("nhwo,nhwi->oi", c.dy[f:e].abs(), xs.abs())
+    _work(c, grouped=True)
+    c.red = [[m * c.u[0], c.u[0], 0, m] for m in c.slots] if uniform else red_table(c.items)
+    return c
+
+
+def check_wg(c, seed_max):
+    check_dy(c)
+    check_mask_bn(c)
+    u = c.unit
+    assert bool((c.dw / u == (c.dw / u).round()).all())
+    assert c.absdw.max() + seed_max < EXACT * u, float(c.absdw.max())
+    for sl in c.slots:
+        assert bool((c.dw[sl] != 0).any((0, 3)).all()), "a tap without a gradient"
+    assert not torch.equal(c.dw[c.slots[0]], c.dw[c.slots[1]])
+    check_work(c, grouped=True)
+    assert [r[3] for r in c.red] == ([0, 1] if c.uniform else [2, 0]) and sum(r[1] for r in c.red) == len(c.items)
+
+
+def grad_layout(widths):
+    """(offsets of the layers' [C][9][C] blocks, row length): G_OFF words, then every block followed by G_GAP words."""
+    offs, o = [], G_OFF
+    for cc in widths:
+        offs.append(o)
+        o += 9 * cc * cc + G_GAP
+    return offs, o
+
+
+def grad_seed(n, seed):
+    """The integer pattern [CAP][n] the gradient rows carry before a launch: 1 .. 9."""
+    return hints((CAP, n), 1, 9, seed)
+
+
+def interleaved_map(jobs):
+    """map rows (job, workgroup, C, dY mode) of one launch, round-robin over its jobs."""
+    out = []
+    for k in range(max(len(j.items) for j in jobs)):
+        out += [[i, k, j.C, j.mode] for i, j in enumerate(jobs) if k < len(j.items)]
+    return out
+
+
+# ------------------------------------------------------------------------------- hand-written slabs
+def int_slabs(cc, n, seed):
+    """[n][slab_elems] float64: integers in [-4, 4], NaN in the duplicate tiles."""
+    valid, _ = slab_index(cc)
+    s = hints((n, slab_elems(cc)), -4, 4, seed)
+    s[:, ~valid] = NAN
+    return s
+
+
+def mant_slabs(shape, seed):
+    """Full-mantissa fp32 values: 24-bit integers from the coordinate hash, scaled by 2^-20 (|x| < 8)."""
+    return ((kx._hash(shape, seed) % (1 << 24)).double() - (1 << 23)) * 2.0 ** -20
+
+
+def conv_reduce_ref(grads, absg, cc, slab, red, g_off):
+    """Add the slabs of every reduce row into grads / their magnitudes into absg ([CAP][row]), in float64."""
+    valid, idx = slab_index(cc)
+    for first, n, _, slot in red:
+        if n == 0:
+            continue
+        part = slab[first:first + n][:, valid]
+        grads[slot].index_add_(0, g_off + idx[valid], part.sum(0))
+        absg[slot].index_add_(0, g_off + idx[valid], part.abs().sum(0))
+
+
+def dense_reduce_ref(grads, absg, kel, slab, red, g_off):
+    for first, n, _, slot in red:
+        grads[slot, g_off:g_off + kel] += slab[first:first + n].sum(0)
+        absg[slot, g_off:g_off + kel] += slab[first:first + n].abs().sum(0)
+
+
+# slab_reduce_all, conv jobs of one launch: (C, [(slot, n slabs)]); a member's slab counts lie on both sides of the
+# bounds of the 4-way unrolled loop (g + 12 < n over 4 thread groups); one row has no slabs, one job a single row
+RED_ALL_CONV = [(64, [(0, 1), (2, 17)]), (32, [(2, 16), (0, 3)]), (16, [(0, 29), (2, 4)]), (16, [(2, 13), (0, 0)]),
+                (32, [(2, 5)])]
+# dense jobs: (kel, [(slot, n slabs)]); kel is no multiple of 32
+RED_ALL_DENSE = [(10, [(0, 1), (2, 33)]), (650, [(2, 8), (0, 57)]), (650, [(0, 9), (2, 25)]), (10, [(2, 32)])]
+RED_ALL_MAX_BLOCKS = 20  # C = 16: 12 chunks (blocks 12 .. 19 exit), C = 64: 144 chunks (a block walks 7 or 8); dense: 21
+RED_ALL_MAX_MEMBERS = 2
+DW_REDUCE = [(16, [(0, 1), (2, 17)]), (32, [(2, 8), (0, 24)]), (64, [(0, 9), (2, 16)])]  # dtf_dw_slab_reduce
+
+
+def red_rows(members):
+    """(first wg, n wgs, 0, slot) rows of members [(slot, n)] whose slabs follow one another."""
+    rows, f = [], 0
+    for slot, n in members:
+        rows.append([f, n, 0, slot])
+        f += n
+    return rows
+
+
+@functools.lru_cache(maxsize=None)
+def reduce_case(conv, dense, full_mantissa=False):
+    """One launch over conv slab jobs ``conv`` and dense jobs ``dense`` (tuples as above): the slabs, reduce tables,
+    gradient offsets, the seeded gradient rows and the float64 result with its summed magnitudes."""
+    k = Case()
+    k.full = full_mantissa
+    k.jobs = []
+    o = G_OFF
+    for i, (cc, members) in enumerate(conv):
+        n = sum(m[1] for m in members)
+        if full_mantissa:
+            valid, _ = slab_index(cc)
+            slab = mant_slabs((n, slab_elems(cc)), 3100 + i)
+            slab[:, ~valid] = NAN
+        else:
+            slab = int_slabs(cc, n, 3000 + i)
+        k.jobs.append(("conv", cc, slab, red_rows(members), o))
+        o += 9 * cc * cc + G_GAP
+    for i, (kel, members) in enumerate(dense):
+        n = sum(m[1] for m in members)
+        slab = mant_slabs((n, kel), 3300 + i) if full_mantissa else hints((n, kel), -4, 4, 3200 + i)
+        k.jobs.append(("dense", kel, slab, red_rows(members), o))
+        o += kel + G_GAP
+    k.row = o
+    k.seed = grad_seed(o, 3400 + len(conv) * 7 + len(dense))
+    k.want, k.mag = k.seed.clone(), k.seed.abs()
+    k.nslab = torch.zeros_like(k.seed)  # slabs summed into each gradient word
+    for kind, w, slab, red, off in k.jobs:
+        (conv_reduce_ref if kind == "conv" else dense_reduce_ref)(k.want, k.mag, w, slab, red, off)
+        for _, n, _, slot in red:
+            k.nslab[slot, off:off + (9 * w * w if kind == "conv" else w)] = n
+    return k
+
+
+def check_reduce_case(k):
+    for kind, w, slab, red, off in k.jobs:
+        if kind == "conv":
+            valid, idx = slab_index(w)
+            assert bool(torch.isnan(slab[:, ~valid]).all()) and not bool(torch.isnan(slab[:, valid]).any())
+            assert sorted(idx[valid].tolist()) == list(range(9 * w * w)), "the slab map is a bijection onto Co x 9 x Ci"
+            assert (int((~valid).sum()) > 0) == (w != 64)
+        else:
+            assert w % 32 != 0 and not bool(torch.isnan(slab).any())
+        assert len({r[3] for r in red}) == len(red) and sum(r[1] for r in red) == slab.shape[0]
+        assert torch.equal(slab.float().double().nan_to_num(), slab.nan_to_num()), "slab words are fp32 values"
+    if not k.full:
+        assert k.mag.max() < EXACT and bool((k.want == k.want.round()).all())
+    assert bool((k.seed != 0).all())

@@ -26,7 +26,8 @@ from typing import Dict, List
 import torch
 
 from .. import ops
-from .hip_step import HipBackend, HipPlan, _log2, _p
+from ..data.datasets import IndexBatch, batch_len
+from .hip_step import HipBackend, HipPlan, PinnedStager, _log2, _p, note_step_advanced, upload_hyper
 
 c_void_p, c_int, c_long, c_float = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_float
 CMAX = 2048
@@ -250,6 +251,7 @@ def _register():
 
 
 class HipImageNetBackend(HipBackend):
+    accepts_index_batches = True  # (the fp32 backend materialises: engine/hip_imagenet_f32.py)
     _plan_cls = None  # _ImageNetPlan (set below); the fp32 backend: engine/hip_imagenet_f32.py
     max_plans = 4
     eval_chunk_env, eval_chunk = "DTF_EVAL_CHUNK_IMAGENET", 64
@@ -314,6 +316,37 @@ class HipImageNetBackend(HipBackend):
             self.ident[:, 0].fill_(1.0)
             self.ident[:, 3].fill_(1.0)
 
+    # --- plans
+    def plan(self, slots, sizes, src=None):
+        """The step plan of this batch composition; ``src``: the dataset whose rows feed it (index batches -- the
+        plan then gathers, crops and resamples inside its graph), part of the key."""
+        if src is None:
+            return super().plan(slots, sizes)
+        key = (tuple(slots), tuple(sizes), id(src))
+        p = self._plans.get(key)
+        if p is None:
+            if len(self._plans) > self.max_plans:
+                self._plans.clear()
+            p = self._plans[key] = self._plan_cls(self, list(slots), list(sizes), src=src)
+        return p
+
+    def train_step(self, slots, batches, hparams, lrs):
+        e = self.e
+        src = None
+        if (self.accepts_index_batches and e.dp is None and batches
+                and all(isinstance(b, IndexBatch) for b in batches) and all(b.ds is batches[0].ds for b in batches)
+                and getattr(batches[0].ds, "imagenet", False) and batches[0].ds.out_size == self.cfg.image_size):
+            src = batches[0].ds  # on-device gather + crop / resample / flip inside the step graph
+        else:
+            batches = [b.materialize() if isinstance(b, IndexBatch) else b for b in batches]
+        sizes = [batch_len(b) for b in batches]
+        p = self.plan(slots, sizes, src)
+        upload_hyper(e, slots, hparams, lrs)
+        p.load_batch(batches)
+        p.run()
+        note_step_advanced(e, slots)
+        return p.loss_sel.clone()  # gathered inside the step graph
+
     @torch.no_grad()
     def infer(self, slot, x):
         """Eval-mode logits of one member on the HIP forward kernels (moving BN statistics)."""
@@ -326,8 +359,11 @@ class HipImageNetBackend(HipBackend):
 
 
 class _ImageNetPlan(HipPlan):
-    def __init__(self, be: HipImageNetBackend, slots: List[int], sizes: List[int], eval_mode: bool = False):
+    def __init__(self, be: HipImageNetBackend, slots: List[int], sizes: List[int], eval_mode: bool = False,
+                 src=None):
         self._init_members(be, slots, sizes, eval_mode)
+        self.src = src  # the dataset of a plan fed index batches (rows -> xin8 inside the graph), else None
+        self._rng_stage = None  # pinned stager of the index-batch rng (made on use)
         e, dev, prog, cfg, N = be.e, be.dev, be.prog, be.cfg, self.N
         bf = self._act_dtype()
         H = cfg.image_size
@@ -335,6 +371,10 @@ class _ImageNetPlan(HipPlan):
         self.x_in = torch.zeros(N, H, H, cfg.in_channels, dtype=torch.float32, device=dev)
         self.labels = torch.zeros(N, dtype=torch.int32, device=dev)
         self.xin8 = torch.zeros(*self._stem_input_shape(N, H), dtype=bf, device=dev)  # stem input (padded / s2d)
+        if src is not None:
+            assert not eval_mode and src.out_size == H
+            self.idx = torch.zeros(N, dtype=torch.long, device=dev)
+            self.rng = torch.zeros(2, dtype=torch.int32, device=dev)
         H1 = H // 2
         H2 = (H1 + 1) // 2
         pool = {}
@@ -706,12 +746,34 @@ class _ImageNetPlan(HipPlan):
                   _p(self.slots_t), ns, _p(be.dense), NPAD_CLS * cfg.final_size)
 
     def prep_input(self):
+        if self.src is not None:
+            self._add("augment", None)  # gather + crop + resample + flip + means + 16-bit stem layout (data.hip)
+            return
         if self.be.s2d:
             self._add(ops.lib().dtf_cg_prep_input_s2d, _p(self.x_in), _p(self.xin8), self.N, self.H, self.H,
                       self.be.cfg.in_channels)
             return
         self._add(ops.lib().dtf_cg_prep_input, _p(self.x_in), _p(self.xin8), self.N * self.H * self.H,
                   self.be.cfg.in_channels)
+
+    def load_batch(self, batches, slots=None):
+        if self.src is None:
+            return super().load_batch(batches, slots)
+        for s, b in zip(self.slots, batches):
+            n, off = len(b), self.first[s]
+            self.idx[off:off + n].copy_(b.idx, non_blocking=True)
+        if self._rng_stage is None:
+            self._rng_stage = PinnedStager(2, torch.int32)
+        self._rng_stage.upload(self.rng, self.src.next_rng())
+
+    def _marker_augment(self, _):
+        """The "augment" marker of a plan fed index batches: dataset rows -> ``xin8`` (the stem's layout, s2d or
+        padded) and ``labels`` in one launch inside the step graph; crops keyed per member (its step counter + the
+        dataset row): placement-invariant (data.hip)."""
+        e, src = self.e, self.src
+        out = dict(out_s2d=self.xin8) if self.be.s2d else dict(out_pad=self.xin8)
+        ops.augment_imagenet(src.train_x, src.train_y, self.idx, self.rng, self.H, True, lab32=self.labels,
+                             member_keys=(self.img_slot, e.state, e.S, 3 * e.Pp + e.R), **out)
 
     def maxpool(self, x, y, H1, H2):
         self._add(ops.lib().dtf_cg_maxpool, _p(x), _p(y), _p(self.am0), None, None, self.N, H1, H1, H2, H2,

@@ -68,6 +68,8 @@ def supports(arch) -> bool:
 class HipImageNetF32Backend(HipImageNetBackend):
     """fp32 bottleneck-ResNet step: the bf16 backend's drivers (train_step, eval, infer) over fp32 plans."""
 
+    accepts_index_batches = False  # index batches are materialised (no in-graph input path for the fp32 step)
+
     def __init__(self, engine):
         _register()
         if not supports(engine.arch):

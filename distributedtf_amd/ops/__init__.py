@@ -289,3 +289,42 @@ def augment_cifar(images, labels, idx, rng, augment=True, out16=None, out32=None
     check(lib().dtf_augment_cifar(ptr(images), ptr(labels), ptr(idx), ptr(rng), n, 1 if augment else 0, ptr(out16),
                                   ptr(out32), ptr(lab32), ptr(lab64), ptr(ks), ptr(kst), int(kstride), int(kcol),
                                   stream()), "augment_cifar")
+
+
+register("dtf_augment_imagenet", [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_long, c_int, c_int, c_int, c_void_p,
+                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_long,
+                                  c_void_p])
+
+
+def augment_imagenet(images, labels, idx, rng, out_size, augment=True, out_s2d=None, out_pad=None, out32=None,
+                     lab32=None, lab64=None, boxes=None, member_keys=None):
+    """Fused gather + random-resized crop (``augment``; else the central crop of side round(0.875 S)) + bilinear
+    resample to ``out_size`` x ``out_size`` + flip + channel-mean subtraction (data.hip).
+
+    images [N,S,S,3] uint8, labels [N] int64, idx [n] int64 (dataset rows), rng [2] int32 (seed, counter; read on
+    the device, so graph replays pick up updates).  Writes any of out_s2d [n,H/2,H/2,16] / out_pad [n,H,H,8] (the two
+    16-bit stem layouts), out32 [n,H,H,3] fp32, lab32 [n] int32, lab64 [n] int64 and boxes [n,5] int32
+    (y0, x0, h, w, flip).  ``member_keys`` as in :func:`augment_cifar`.
+    """
+    H = int(out_size)
+    assert images.dtype == torch.uint8 and images.dim() == 4 and images.shape[3] == 3 and images.is_contiguous()
+    S = int(images.shape[1])
+    assert images.shape[2] == S and 1 <= S <= 4096, "square stored images up to 4096"
+    assert H >= 2 and H % 2 == 0 and H <= 1024 and (2 * H + 1) * S < 2 ** 23, "output size: even, (2H+1) S < 2^23"
+    assert labels.dtype == torch.int64 and labels.numel() == images.shape[0] and idx.dtype == torch.int64
+    assert idx.is_contiguous() and rng.numel() >= 2 and rng.dtype == torch.int32
+    n = int(idx.numel())
+    for t, shp, dt in ((out_s2d, (H // 2, H // 2, 16), act_dtype()), (out_pad, (H, H, 8), act_dtype()),
+                       (out32, (H, H, 3), torch.float32)):
+        if t is not None:
+            assert t.dtype == dt and t.shape[0] >= n and tuple(t.shape[1:]) == shp and t.is_contiguous()
+    for t, dt, per in ((lab32, torch.int32, 1), (lab64, torch.int64, 1), (boxes, torch.int32, 5)):
+        if t is not None:
+            assert t.dtype == dt and t.numel() >= n * per and t.is_contiguous()
+    ks, kst, kstride, kcol = member_keys if member_keys is not None else (None, None, 0, 0)
+    if ks is not None:
+        assert ks.dtype == torch.int32 and ks.numel() >= n and kst.dtype == torch.float32
+    check(lib().dtf_augment_imagenet(ptr(images), ptr(labels), ptr(idx), ptr(rng), n, int(images.shape[0]), S, H,
+                                     1 if augment else 0, ptr(out_s2d), ptr(out_pad), ptr(out32), ptr(lab32),
+                                     ptr(lab64), ptr(boxes), ptr(ks), ptr(kst), int(kstride), int(kcol), stream()),
+          "augment_imagenet")

@@ -137,7 +137,10 @@ def build_parser(defaults: Optional[Dict[str, Any]] = None) -> argparse.Argument
     p.add_argument("--resnet_version", type=int, default=2, choices=[1, 2])
     p.add_argument("--data_dir", default=None)
     p.add_argument("--use_synthetic_data", type=_synthetic, default=None,
-                   help="true / false (reference flag) or 'learnable' (CIFAR: class-template images, real input path)")
+                   help="true / false (reference flag) or 'learnable' (cifar10 / imagenet: class-template images, real input path)")
+    p.add_argument("--image_size", type=int, default=None,
+                   help="imagenet: the model's input side (default 224; a multiple of 32): real and learnable images "
+                        "are cropped and resampled to it")
     p.add_argument("--max_train_steps", type=int, default=None)
     p.add_argument("--debug_steps", type=int, default=None, help="MNIST: steps per 'epoch' (reference used 10)")
     p.add_argument("--batch_size", type=int, default=None, help="override every member's batch_size")
@@ -217,6 +220,8 @@ class MainArgs(argparse.Namespace):
             if self.resnet_size:
                 kw["resnet_size"] = self.resnet_size
             kw["resnet_version"] = self.resnet_version
+        if self.model == "imagenet" and getattr(self, "image_size", None):
+            kw["image_size"] = self.image_size
         if self.model == "mnist" and self.debug_steps:
             kw["debug_steps"] = self.debug_steps
         if self.model == "mnist":

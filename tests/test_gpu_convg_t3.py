@@ -7,6 +7,8 @@ BN-backward statistics) at every instantiated geometry: 56 x 56 x 64 (8-row tile
 The folded forward (``dtf_convg_t3`` mode 1, convg_t3_kernel XF: relu(x * scale + shift) applied while the input rows
 are staged, padding left zero) at the same geometries is compared bitwise with a float64 reference on small-integer
 operands (tests/_convg_exact.py ``t3_fold_case``: |y| <= 256 and sum(y^2) < 2^24 are asserted on the reference first).
+So are the plain (mode 0) forward and the data gradient (EPI 6, akm = 1) with both statistics rows
+(tests/_convg_fwd_exact.py ``t3_case``); ``test_convg_t3_matches_torch`` keeps the full-mantissa comparison.
 """
 import ctypes
 
@@ -129,3 +131,56 @@ def test_convg_t3_folded_forward_is_exact(hw, c, flags):
         pytest.fail("%d outputs differ; first: image %d row %d column %d channel %d: got %r want %r" % (
             bad.shape[0], i, r, col, o, float(got[i, r, col, o]), float(k.y[i, r, col, o])))
     assert torch.equal(cx.acc_download(st, cx.FX_STAT, det), k.st.float())
+
+
+@pytest.mark.parametrize("hw,c", [(56, 64), (28, 128), (14, 256)])
+@pytest.mark.parametrize("dgrad", [False, True])
+@pytest.mark.parametrize("flags", [1, 0])
+def test_convg_t3_plain_is_exact(hw, c, dgrad, flags):
+    """mode 0: the forward (EPI 4) and the data gradient (EPI 6, akm = 1: taps flipped over the forward weight layout,
+    mask by BN(xm) > 0, sums dz and dz xhat) of members in slots 0 and 2 (capacity 3) equal the float64 reference bit
+    for bit (tests/_convg_fwd_exact.py ``t3_case``); the statistics rows are pre-seeded with integers, the idle
+    slot's row and the columns past the channel count stay as seeded, the idle slot's weights and coefficients are
+    NaN and the output sits between canary guards."""
+    import _convg_exact as cx
+    import _convg_fwd_exact as fx
+    ops, hi, dev, det = cx.gpu_env()
+    k = fx.t3_case(hw, c, dgrad)
+    dt = ops.act_dtype()
+    fx.check_t3(k, dt)  # the reference alone
+    n = k.x.shape[0]
+    xd, wd, xmd, epd = k.x.to(dt).to(dev), k.w.to(dt).to(dev), k.xm.to(dt).to(dev), k.c_ep.float().to(dev)
+    ybuf, y = fx.guarded((n, hw, hw, c), cx.Y_CANARY, dt, dev)
+    shift = cx.FX_GRAD if dgrad else cx.FX_STAT
+    st = cx.acc_upload(k.seed_st, shift, det, dev)
+    rows = hi._CG_T3[hw]
+    tc = 64 if hw == 56 else 128
+    items = [[s, (img * hw + y0) * hw, (img * hw + y0 + rows) * hw, o0] for s, f, e in fx.T3_RANGES
+             for img in range(f, e) for y0 in range(0, hw, rows) for o0 in range(0, c, tc)]
+    work = torch.tensor(items, dtype=torch.int32, device=dev)
+    a = hi.CgArgs()
+    a.x, a.y, a.w, a.work, a.st_out = xd.data_ptr(), y.data_ptr(), wd.data_ptr(), work.data_ptr(), st.data_ptr()
+    a.w_mstride, a.w_off = c * 9 * c, 0
+    a.Hi = a.Wi = a.Ho = a.Wo = hw
+    a.Ci = a.Co = c
+    a.kh = a.kw = 3
+    a.stride, a.pad, a.cmax, a.log2ci, a.flags = 1, 1, cx.CMAX, c.bit_length() - 1, flags
+    if dgrad:
+        a.xm, a.c_ep = xmd.data_ptr(), epd.data_ptr()
+    rc = ops.lib().dtf_convg_t3(ctypes.byref(a), tc, 6 if dgrad else 4, int(dgrad), hw, work.shape[0], 0, ops.stream())
+    assert rc == 0, rc
+    torch.cuda.synchronize()
+    got = y.cpu().double()
+    if not torch.equal(got, k.y):
+        bad = (got != k.y).nonzero()
+        i, r, col, o = (int(v) for v in bad[0])
+        pytest.fail("%d outputs differ; first: image %d row %d column %d channel %d: got %r want %r" % (
+            bad.shape[0], i, r, col, o, float(got[i, r, col, o]), float(k.y[i, r, col, o])))
+    g = fx.GUARD
+    assert bool((ybuf[:g] == cx.Y_CANARY).all()) and bool((ybuf[-g:] == cx.Y_CANARY).all())
+    gs = cx.acc_download(st, shift, det)
+    if not torch.equal(gs, k.st.float()):
+        bad = (gs != k.st.float()).nonzero()
+        s, r, o = (int(v) for v in bad[0])
+        pytest.fail("%d statistics differ; first: slot %d row %d channel %d: got %r want %r" % (
+            bad.shape[0], s, r, o, float(gs[s, r, o]), float(k.st[s, r, o])))

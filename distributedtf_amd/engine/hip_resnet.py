@@ -8,14 +8,16 @@ concatenated along N, ``img_slot`` maps image -> member row):
   memset       BN statistic accumulators, loss
   prep_input   fp32 NHWC images -> bf16, channels padded 3 -> 16
   stem         conv_fwd (no input BN)                           -> x0, stats(x0)
-  per block    [proj conv_fwd 1x1 (BN1+ReLU prologue)]          -> sc
-               conv_fwd 3x3 (BN1+ReLU prologue)                 -> h,  stats(h)
+  per block    conv_fwd 3x3 (BN1+ReLU prologue)                 -> h,  stats(h)
+               [+ the 1x1 projection shortcut, in the same launch from the staged tile's centre tap -> sc]
                conv_fwd 3x3 (BN2+ReLU prologue, + residual)     -> x', stats(x')
   head         final BN+ReLU, GAP, dense, softmax-CE, dense grads, BN-final reductions
   bn_running   moving averages of every BN of every member
   backward     head_bwd_apply -> g_L; per block (reverse): conv_b dgrad (+relu mask, BN2 reductions),
                conv_b wgrad, [proj dgrad + wgrad], conv_a dgrad (BN2-backward prologue, relu mask,
-               BN1 reductions), conv_a wgrad, bn_bwd_apply (+ identity residual) -> g_{l}; stem wgrad
+               BN1 reductions), conv_a wgrad, BN1-backward (+ identity residual) -> g_{l}, folded into the dY
+               staging of the previous block's conv_b backward; stem wgrad (block 0's BN1-backward applied to its
+               dY operand on load)
   optimizer    one fused launch over all members (engine/optim.py semantics), zeroes grads
 
 The whole sequence is captured once per batch composition into a HIP graph
@@ -137,6 +139,7 @@ class ConvArgs(ctypes.Structure):
         ("x3", c_void_p), ("xout", c_void_p), ("rslab", c_void_p), ("rtab", c_void_p), ("r_goff", c_long),
         ("r_c", c_int), ("r_nblk", c_int), ("n_main", c_int),
         ("u_items", c_int), ("u_chunk", c_int), ("u_per", c_int), ("u_pad", c_int),
+        ("y2", c_void_p), ("w2_off", c_long),
     ]
 
 
@@ -757,7 +760,8 @@ class _StepPlan(HipPlan):
             return
         super()._add(fn, *args)
 
-    def _conv_fwd(self, ci, x, y, stats_bn, in_bn, res=None):
+    def _conv_fwd(self, ci, x, y, stats_bn, in_bn, res=None, proj=None):
+        """proj = (projection conv, its output): the block's 1x1 shortcut computed by this (conv_a's) launch."""
         be, L = self.be, self.be.L
         c = L.prog.convs[ci]
         Hi = x.shape[1]
@@ -791,6 +795,11 @@ class _StepPlan(HipPlan):
         if stats_bn is not None:
             a.st_out = _p(self._st_w(stats_bn))
         a.Hi, a.Wi, a.Ho, a.Wo, a.rows = Hi, Hi, Ho, Ho, rows
+        if proj is not None:
+            cp = L.prog.convs[proj[0]]
+            assert (cp.k, cp.stride, cp.cin, cp.cout) == (1, c.stride, c.cin, c.cout) and c.k == 3, (ci, proj[0])
+            assert proj[1].shape == y.shape and in_bn is not None and res is None
+            a.y2, a.w2_off = _p(proj[1]), L.fwd_off[proj[0]]
         rows_in = (rows - 1) * c.stride + c.k
         tsz = (rows_in * (Hi + 2 * P) * max(_cpad(cin), _cpad_fwd(cin)) + 8 + 63) // 64 * 64
         lds = 1280 + 2 * tsz * 2
@@ -1306,6 +1315,7 @@ class _StepPlan(HipPlan):
                   e.S, ha.gamma_off, ha.beta_off, _p(be.st_f(fb)), _p(be.st_b(fb)), _p(self.cnt), hw,
                   cfg.final_size, N)
         pend = None  # deferred BN1-backward of the block just processed: (dz1, x, add, out, bn1)
+        stem_dy = None  # block 0 with a projection shortcut: (dz1, x, bn1) of the BN1-backward the stem wgrad applies
         for i in range(nblk - 1, -1, -1):
             blk = prog.blocks[i]
             bn1, bn2 = blk.bns
@@ -1353,17 +1363,25 @@ class _StepPlan(HipPlan):
                                  in_bn=bn2, res=pd, xm=x, ep_bn=bn1)
                 self._conv_wgrad(ca, x, T["dz2"], mode_x=1, mode_dy=2, x_bn=bn1, dy_bn=bn2, dy2=h)
             # g_in = BN1-backward(dz1, x) [+ g_out if identity shortcut]
+            add = None if blk.proj is not None else g_cur
+            if i == 0 and add is None:
+                stem_dy = (Tin["dz1"], x, bn1)  # g = BN1-backward(dz1, x) has one reader: the stem wgrad
+                break
             g_next = Tin["g"][1] if g_cur is Tin["g"][0] else Tin["g"][0]
             if x.shape[3] in self.defer_cs:  # g (read by the previous block's deferred conv_b wgrad) stays alive
                 g_next = self._fresh_like(Tin["g"][0])
-            add = None if blk.proj is not None else g_cur
             if i > 0:
                 pend = (Tin["dz1"], x, add, g_next, bn1)
             else:
                 self._bn_bwd_apply(Tin["dz1"], x, add, g_next, bn1)
             g_cur = g_next
         # stem wgrad (input = padded image, real channels 3)
-        self._conv_wgrad(prog.stem, self.xin16, g_cur, mode_x=0, mode_dy=0, cin_real=cfg.in_channels)
+        if stem_dy is not None:  # block 0's BN1-backward applied to the dY operand on load: no g pass, no g buffer
+            dz1, x0, bn1 = stem_dy
+            self._conv_wgrad(prog.stem, self.xin16, dz1, mode_x=0, mode_dy=2, dy_bn=bn1, dy2=x0,
+                             cin_real=cfg.in_channels)
+        else:
+            self._conv_wgrad(prog.stem, self.xin16, g_cur, mode_x=0, mode_dy=0, cin_real=cfg.in_channels)
         self._emit_deferred_wgrad()
         self._step_epilogue()
 
@@ -1377,9 +1395,9 @@ class _StepPlan(HipPlan):
             bn1, bn2 = blk.bns
             nxt = prog.blocks[i + 1].bns[0] if i + 1 < nblk else prog.final_bn
             x, h, y = self.xs[i], self.hs[i], self.xs[i + 1]
-            if blk.proj is not None:
-                self._conv_fwd(blk.proj, x, self.scs[i], stats_bn=None, in_bn=bn1)
-            self._conv_fwd(blk.convs[0], x, h, stats_bn=bn2, in_bn=bn1)
+            # (the projection shortcut reads the same BN1+ReLU input: conv_a's launch computes it too)
+            self._conv_fwd(blk.convs[0], x, h, stats_bn=bn2, in_bn=bn1,
+                           proj=(blk.proj, self.scs[i]) if blk.proj is not None else None)
             res = self.scs[i] if blk.proj is not None else x
             self._conv_fwd(blk.convs[1], h, y, stats_bn=nxt, in_bn=bn2, res=res)
 

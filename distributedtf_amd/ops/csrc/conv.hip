@@ -133,6 +133,10 @@ struct ConvArgs {
   // is arithmetic -- member b / u_items, iterations [k * u_chunk, ...) of its u_per -- instead of a dependent
   // load of work[b] (one memory round trip less before every address of the kernel).  u_items = 0: use `work`.
   int u_items, u_chunk, u_per, u_pad;
+  // fwd, PROJ instantiations: the block's 1x1 projection shortcut computed from conv_a's staged tile (centre tap of
+  // the 3x3 window = the pixel a 1x1 conv of the same stride samples).  y2 null: no projection.
+  bf16_t* y2;               // projection output (conv_a's output geometry, no statistics, no residual)
+  long w2_off;              // projection weights (OHWI, [COUT][CIN]) in the forward weight row (w, w_mstride)
 };
 
 __device__ __forceinline__ int4 work_item_at(const ConvArgs& a, int b) {
@@ -954,8 +958,15 @@ struct Stage {
 
 constexpr int MAXT = 4;  // output tiles per wave per iteration (host-checked)
 
-template <int CIN, int COUT, int S, int K, int MODE_IN, bool RESID, bool STATS>
+// PROJ: also the block's 1x1 projection shortcut (same stride, same input transform) -> a.y2.  The pixel it samples
+// is the centre tap of the 3x3 window, and that tap's CIN channels are exactly the first CIN / 8 lane groups of
+// k-step PS = 4 * CIN / 32 (k = tap * CIN + c): one more MFMA per output tile on the B operand already gathered for
+// that step, against projection weights that are zero in the other lane groups (the k-chunks the standalone 1x1
+// launch pads with zeros) -- the same products, k order and rounding point as that launch.
+template <int CIN, int COUT, int S, int K, int MODE_IN, bool RESID, bool STATS, bool PROJ = false>
 __global__ __launch_bounds__(256) void conv_fwd_kernel(ConvArgs a) {
+  static_assert(!PROJ || (K == 3 && (CIN == 16 || CIN == 32)), "projection: centre tap of a 3x3 window, one k-step");
+  constexpr int PS = 4 * CIN / 32;  // PROJ: the k-step whose leading lane groups hold the centre tap
   constexpr int NT = COUT / 16;
   constexpr int WPT = 4 / NT;
   constexpr int KTOT = K * K * CIN;
@@ -985,6 +996,13 @@ __global__ __launch_bounds__(256) void conv_fwd_kernel(ConvArgs a) {
       if (k0 < KTOT) v = *reinterpret_cast<const bf16x8_t*>(wb + k0);
       afr[s] = v;
     }
+  }
+  [[maybe_unused]] bf16x8_t pfr;  // PROJ: the 1x1 weights of this wave's channel tile (k-chunks >= CIN zero)
+  if constexpr (PROJ) {
+    pfr = (bf16x8_t){0, 0, 0, 0, 0, 0, 0, 0};
+    if (8 * (lane >> 4) < CIN)
+      pfr = *reinterpret_cast<const bf16x8_t*>(a.w + (long)slot * a.w_mstride + a.w2_off +
+                                               (long)(ct * 16 + (lane & 15)) * CIN + 8 * (lane >> 4));
   }
   const int rows = a.rows;
   const int bands = a.Ho / rows;
@@ -1044,11 +1062,15 @@ __global__ __launch_bounds__(256) void conv_fwd_kernel(ConvArgs a) {
       uint2 r = make_uint2(0, 0);
       if constexpr (RESID) r = rres[i];
       const bf16_t* tb = tile + (oy * S * wp + ox * S) * cpad<CIN>();
+      [[maybe_unused]] f32x4_t pa;
 #pragma unroll
       for (int s = 0; s < KS; ++s) {
         bf16x8_t b = {0, 0, 0, 0, 0, 0, 0, 0};
         if (32 * s + 8 * (lane >> 4) < KTOT) b = *reinterpret_cast<const bf16x8_t*>(tb + tapoff[s]);
         acc = mfma16(afr[s], b, acc);
+        if constexpr (PROJ) {
+          if (s == PS) pa = mfma16(pfr, b, (f32x4_t){0.f, 0.f, 0.f, 0.f});
+        }
       }
       float v[4] = {acc[0], acc[1], acc[2], acc[3]};
       if constexpr (RESID) {
@@ -1061,6 +1083,12 @@ __global__ __launch_bounds__(256) void conv_fwd_kernel(ConvArgs a) {
       pk.x = pack2bf(v[0], v[1]);
       pk.y = pack2bf(v[2], v[3]);
       st_act8(a.y + o, pk);
+      if constexpr (PROJ) {
+        uint2 pp;
+        pp.x = pack2bf(pa[0], pa[1]);
+        pp.y = pack2bf(pa[2], pa[3]);
+        st_act8(a.y2 + o, pp);
+      }
       if constexpr (STATS) {
         const float r0 = bf2f((bf16_t)(pk.x & 0xffff)), r1 = bf2f((bf16_t)(pk.x >> 16));
         const float r2 = bf2f((bf16_t)(pk.y & 0xffff)), r3 = bf2f((bf16_t)(pk.y >> 16));
@@ -1086,8 +1114,11 @@ __global__ __launch_bounds__(256) void conv_fwd_kernel(ConvArgs a) {
 // geometry (W = H = 512/C, 8-row bands), uniform-base + 32-bit lane offsets and packed epilogue math
 // (same scheme as conv_bwd_fused_kernel).
 // single member's 8x8 C = 64 layer (one image per item) launches 256 workgroups instead of 128.
-template <int C, int MODE_IN, bool RESID, int ROWS = 8>
+// PROJ (C = 16, block 0): also the 16 -> 16 1x1 projection shortcut -> a.y2, from k-step 2's B operand (see
+// conv_fwd_kernel).
+template <int C, int MODE_IN, bool RESID, int ROWS = 8, bool PROJ = false>
 __device__ __forceinline__ void conv_fwd_s1_body(const ConvArgs& a, const int bid, char* smem) {
+  static_assert(!PROJ || (C == 16 && MODE_IN == 1 && !RESID), "projection: block 0 of the C = 16 stage");
   constexpr int W = 512 / C, H = W, BANDS = H / ROWS;
   constexpr int NT = C / 16, WPT = 4 / NT;  // NT: output-channel tiles
   constexpr int KTOT = 9 * C, KS = (KTOT + 31) / 32;
@@ -1145,6 +1176,13 @@ __device__ __forceinline__ void conv_fwd_s1_body(const ConvArgs& a, const int bi
       if (k0 < KTOT) v = *reinterpret_cast<const bf16x8_t*>(wb + k0);
       afr[s] = v;
     }
+  }
+  [[maybe_unused]] bf16x8_t pfr;  // PROJ: the 1x1 weights [co][ci] (k-chunks >= C zero)
+  if constexpr (PROJ) {
+    pfr = (bf16x8_t){0, 0, 0, 0, 0, 0, 0, 0};
+    if (8 * (lane >> 4) < C)
+      pfr = *reinterpret_cast<const bf16x8_t*>(wgt + (long)slot * w_mstride + a.w2_off +
+                                               (long)(ct * 16 + (lane & 15)) * C + 8 * (lane >> 4));
   }
   coef_reduce<C, MODE_IN == 0 ? 0 : 1>(cl);
   coef_finish<C, MODE_IN == 0 ? 0 : 1>(coef, cl, n_in);
@@ -1213,9 +1251,15 @@ __device__ __forceinline__ void conv_fwd_s1_body(const ConvArgs& a, const int bi
 #pragma unroll
     for (int i = 0; i < MT; ++i) {
       f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
+      [[maybe_unused]] f32x4_t pa;
 #pragma unroll
-      for (int s = 0; s < KS; ++s)
-        acc = mfma16(afr[s], *reinterpret_cast<const bf16x8_t*>(tile + tbo[i] + tapoff[s]), acc);
+      for (int s = 0; s < KS; ++s) {
+        const bf16x8_t b = *reinterpret_cast<const bf16x8_t*>(tile + tbo[i] + tapoff[s]);
+        acc = mfma16(afr[s], b, acc);
+        if constexpr (PROJ) {
+          if (s == 4 * C / 32) pa = mfma16(pfr, b, (f32x4_t){0.f, 0.f, 0.f, 0.f});
+        }
+      }
       f32x2_t v0 = {acc[0], acc[1]}, v1 = {acc[2], acc[3]};
       if constexpr (RESID) {
         v0 += unpk2(rres[i].x);
@@ -1225,6 +1269,12 @@ __device__ __forceinline__ void conv_fwd_s1_body(const ConvArgs& a, const int bi
       pk.x = pk2(v0);
       pk.y = pk2(v1);
       st_act8(a.y + band + pofs[i], pk);
+      if constexpr (PROJ) {
+        uint2 pp;
+        pp.x = pk2((f32x2_t){pa[0], pa[1]});
+        pp.y = pk2((f32x2_t){pa[2], pa[3]});
+        st_act8(a.y2 + band + pofs[i], pp);
+      }
       const f32x2_t r0v = unpk2(pk.x), r1v = unpk2(pk.y);
       ssum[0] += r0v;
       ssum[1] += r1v;
@@ -1250,10 +1300,10 @@ __device__ __forceinline__ void conv_fwd_s1_body(const ConvArgs& a, const int bi
   STAMP_FLUSH(a.cin_real, nit);
 }
 
-template <int C, int MODE_IN, bool RESID, int ROWS = 8>
+template <int C, int MODE_IN, bool RESID, int ROWS = 8, bool PROJ = false>
 __global__ __launch_bounds__(256) void conv_fwd_s1_kernel(ConvArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  conv_fwd_s1_body<C, MODE_IN, RESID, ROWS>(a, (int)blockIdx.x, smem);
+  conv_fwd_s1_body<C, MODE_IN, RESID, ROWS, PROJ>(a, (int)blockIdx.x, smem);
 }
 
 // ---------------------------------------------------------------------------------- dgrad
@@ -2351,6 +2401,11 @@ int launch(KernelT k, int nblocks, size_t lds, hipStream_t st, const ConvArgs& a
 DTF_API int dtf_conv_fwd_s1(const ConvArgs* args, int c, int mode, int resid, int rows, int nblocks, int lds,
                             hipStream_t stream) {
   DTF_HOST_CHECK(args->rows == rows);
+  if (args->y2 != nullptr) {  // + projection shortcut: block 0 of the C = 16 stage only
+    if (c == 16 && mode == 1 && resid == 0 && rows == 8 && DTF_ALIGNED16(args->y2))
+      return launch(conv_fwd_s1_kernel<16, 1, false, 8, true>, nblocks, lds, stream, *args);
+    return -1;
+  }
   if (rows == 4) {
     if (c == 64 && mode == 1 && resid == 0) return launch(conv_fwd_s1_kernel<64, 1, false, 4>, nblocks, lds, stream, *args);
     if (c == 64 && mode == 1 && resid == 1) return launch(conv_fwd_s1_kernel<64, 1, true, 4>, nblocks, lds, stream, *args);
@@ -2444,6 +2499,14 @@ DTF_API int dtf_wpitch(int c) { return c == 16 ? wpitch<16>() : c == 32 ? wpitch
 
 DTF_API int dtf_conv_fwd(const ConvArgs* args, int cin, int cout, int s, int k, int mode, int resid, int stats,
                          int nblocks, int lds, hipStream_t stream) {
+  if (args->y2 != nullptr) {  // conv_a of a stage transition + its projection shortcut
+    if (!(k == 3 && s == 2 && mode == 1 && resid == 0 && stats == 1 && DTF_ALIGNED16(args->y2))) return -1;
+    if (cin == 16 && cout == 32)
+      return launch(conv_fwd_kernel<16, 32, 2, 3, 1, false, true, true>, nblocks, lds, stream, *args);
+    if (cin == 32 && cout == 64)
+      return launch(conv_fwd_kernel<32, 64, 2, 3, 1, false, true, true>, nblocks, lds, stream, *args);
+    return -1;
+  }
   // stem (input padded to 16 channels, no input BN)
   FWD_CASE(16, 16, 1, 3, 0, false, true)
   // stage convs: conv_a (BN1+ReLU on the block input), conv_b (BN2+ReLU, + residual)

@@ -171,7 +171,7 @@ def imagenet_arrays_available(data_dir: Optional[str]) -> bool:
 
 
 def load_imagenet_arrays(data_dir: str, device=None, max_bytes: Optional[int] = None,
-                         out_size: Optional[int] = None):
+                         out_size: Optional[int] = None, resident: bool = True, stage_rows: int = 1024):
     """Pre-decoded ImageNet-style arrays: ``train_images.npy`` / ``val_images.npy`` uint8 [N, S, S, 3] (NHWC, one
     square stored side S for both) and ``train_labels.npy`` / ``val_labels.npy`` integer [N].  The files are memory
     mapped (``np.load(mmap_mode="r")``), so validation reads only their headers.  The arrays are meant to live on
@@ -179,6 +179,9 @@ def load_imagenet_arrays(data_dir: str, device=None, max_bytes: Optional[int] = 
     ``eval_set`` at ``out_size`` (the stored side if not given) -- are checked against the device's free memory (or
     ``max_bytes``) and a MemoryError is raised before anything is allocated.  The step's own buffers are not
     counted: the check catches a set that cannot fit at all, not one that leaves too little for a large batch.
+    ``resident=False`` (HostImageNetDataset): the training images stay in the memory-mapped file on the host and are
+    not counted; the validation images, the labels, the evaluation cache and the two staging halves of ``stage_rows``
+    images each (2 * stage_rows * S * S * 3 bytes, RowStager) are.
     Returns (train_x, train_y, val_x, val_y) as memory-mapped numpy arrays."""
     if not imagenet_arrays_available(data_dir):
         raise FileNotFoundError("ImageNet arrays (%s) not found under %s" % (", ".join(IMAGENET_FILES), data_dir))
@@ -209,6 +212,16 @@ def load_imagenet_arrays(data_dir: str, device=None, max_bytes: Optional[int] = 
     limit = max_bytes
     if limit is None and device is not None and torch.device(device).type == "cuda":
         limit = int(torch.cuda.mem_get_info(torch.device(device))[0])
+    if not resident:
+        stage = 2 * int(stage_rows) * int(trx.shape[1]) * int(trx.shape[1]) * 3
+        need = need - int(trx.size) + stage
+        if limit is not None and need > limit:
+            raise MemoryError("ImageNet arrays under %s with the training images on the host need %.1f GB on the "
+                              "device (%d validation images at %d x %d with the fp32 evaluation cache, the labels and "
+                              "%.1f GB of staging for %d rows per step) but %.1f GB are free: store fewer validation "
+                              "images" % (data_dir, need / 1e9, vax.shape[0], trx.shape[1], trx.shape[1], stage / 1e9,
+                                          int(stage_rows), limit / 1e9))
+        return trx, tr_y, vax, va_y
     if limit is not None and need > limit:
         raise MemoryError("ImageNet arrays under %s need %.1f GB on the device (%d + %d images at %d x %d, with the "
                           "fp32 evaluation cache) but %.1f GB are free: store the images at a smaller side"
@@ -366,8 +379,11 @@ class IndexBatch:
     :meth:`materialize`.
     """
 
-    def __init__(self, ds: "DeviceDataset", idx: torch.Tensor):
+    def __init__(self, ds: "DeviceDataset", idx: torch.Tensor, next_rows: Optional[torch.Tensor] = None):
         self.ds, self.idx = ds, idx
+        # host-resident sets: the rows the member will ask for next (a hint the plan prefetches by and verifies on
+        # the next step; None: nothing announced, e.g. at an epoch end)
+        self.next_rows = next_rows
 
     def __len__(self):
         return int(self.idx.numel())
@@ -394,16 +410,9 @@ class DeviceDataset:
     def __init__(self, train_x, train_y, test_x, test_y, device, augment=None, eval_transform=None, seed=0,
                  out_size=None):
         self.train_x = torch.as_tensor(train_x).to(device).contiguous()
-        self.train_y = torch.as_tensor(train_y).to(device).long().contiguous()
-        self.test_x = torch.as_tensor(test_x).to(device).contiguous()
-        self.test_y = torch.as_tensor(test_y).to(device).long().contiguous()
-        self.augment = augment
-        self.eval_transform = eval_transform
-        self._eval_cache = None
-        self.device = torch.device(device)
+        self._init_rest(train_y, test_x, test_y, device, augment, eval_transform, seed, out_size)
         self.hip_augment = (self.device.type == "cuda" and augment is augment_cifar
                             and self.train_x.dtype == torch.uint8 and tuple(self.train_x.shape[1:]) == (32, 32, 3))
-        self.out_size = int(out_size) if out_size else None
         sq = self.train_x.dim() == 4 and self.train_x.shape[1] == self.train_x.shape[2] and self.train_x.shape[3] == 3
         self.imagenet = (augment is augment_imagenet and self.out_size is not None
                          and self.train_x.dtype == torch.uint8 and sq)
@@ -411,8 +420,23 @@ class DeviceDataset:
             raise ValueError("augment_imagenet needs square uint8 [N, S, S, 3] images and an out_size")
         if self.imagenet and self.device.type == "cuda":
             self.hip_augment = True
+
+    def _init_rest(self, train_y, test_x, test_y, device, augment, eval_transform, seed, out_size):
+        """Everything but the training images, which a subclass may keep elsewhere (HostImageNetDataset): labels and
+        the evaluation set on the device, the transforms, the evaluation cache, the augmentation rng."""
+        self.train_y = torch.as_tensor(train_y).to(device).long().contiguous()
+        self.test_x = torch.as_tensor(test_x).to(device).contiguous()
+        self.test_y = torch.as_tensor(test_y).to(device).long().contiguous()
+        self.augment = augment
+        self.eval_transform = eval_transform
+        self._eval_cache = None
+        self.device = torch.device(device)
+        self.out_size = int(out_size) if out_size else None
         self.rng_seed = int(seed) & 0x7FFFFFFF
         self.rng_counter = 0
+
+    def close(self) -> None:
+        """Release what the set holds besides memory (the gather threads of a host-resident set); idempotent."""
 
     @property
     def num_train(self):
@@ -468,6 +492,266 @@ class DeviceDataset:
             x = self.eval_transform(x) if self.eval_transform is not None else x.float()
             self._eval_cache = (x, self.test_y)
         return self._eval_cache
+
+
+def _stager_worker(jobs):
+    """A gather thread of a RowStager: runs queued callables until it reads None.  It holds the queue only, never
+    the stager, so a dropped stager is collected and closes its threads."""
+    while True:
+        job = jobs.get()
+        if job is None:
+            return
+        job()
+
+
+class RowStager:
+    """Rows of a host-resident uint8 image array [N, S, S, 3] -> one of two device staging halves.
+
+    Holds two pinned host buffers [cap, S, S, 3], the device tensor ``dev`` [2, cap, S, S, 3], a copy stream and per
+    half a "copied" and a "consumed" event.  ``stage(rows, half)`` returns at once: gather threads (at most
+    ``min(8, torch.get_num_threads())``, daemons) copy ``images[rows]`` into the half's pinned buffer, one slice of
+    the rows each (``np.take(..., out=...)``, which releases the interpreter lock); the thread that finishes last
+    issues one non-blocking host-to-device copy on the copy stream -- after that stream has waited for the half's
+    "consumed" event -- and records "copied".  The pinned buffer is not overwritten before the copy that last read
+    it is done.  ``wait_copied(half)`` makes the current stream wait for the half, ``mark_consumed(half)`` records on
+    the current stream that the half's reader is enqueued.  On a CPU device the same code runs without streams and
+    events.  ``cap`` grows on demand (``ensure``: both halves are reallocated after one device synchronise and
+    ``generation`` advances -- whoever baked ``dev``'s address into a captured graph must capture again)."""
+
+    def __init__(self, images, device, threads: Optional[int] = None):
+        import queue
+        import threading
+        assert isinstance(images, np.ndarray) and images.dtype == np.uint8 and images.ndim == 4
+        self.images = images
+        self.device = torch.device(device)
+        self.cuda = self.device.type == "cuda"
+        self.S = int(images.shape[1])
+        self.cap, self.generation = 0, 0
+        self.host, self.dev = [None, None], None
+        self.copy_stream = torch.cuda.Stream(self.device) if self.cuda else None
+        self.copied = self.consumed = (None, None)
+        self.stages = 0  # stage() calls
+        k = max(1, min(8, int(threads) if threads else torch.get_num_threads()))
+        self._jobs = queue.SimpleQueue()
+        self._threads = [threading.Thread(target=_stager_worker, args=(self._jobs,), daemon=True,
+                                          name="dtf-row-stager-%d" % i) for i in range(k)]
+        for t in self._threads:
+            t.start()
+        self._issued = [None, None]  # per half: the last job's (done Event, error list)
+        self._closed = False
+
+    # ---- buffers
+    def ensure(self, cap: int) -> None:
+        cap = int(cap)
+        if cap <= self.cap:
+            return
+        self.drain()
+        shape = (cap, self.S, self.S, 3)
+        if self.cuda:
+            torch.cuda.synchronize(self.device)  # once: nothing enqueued reads the old halves any more
+            self.host = [torch.empty(shape, dtype=torch.uint8).pin_memory() for _ in range(2)]
+            self.copied = tuple(torch.cuda.Event() for _ in range(2))
+            self.consumed = tuple(torch.cuda.Event() for _ in range(2))
+        else:
+            self.host = [torch.empty(shape, dtype=torch.uint8) for _ in range(2)]
+        self.dev = torch.empty((2,) + shape, dtype=torch.uint8, device=self.device)
+        self.cap = cap
+        self.generation += 1
+
+    @property
+    def nbytes(self) -> int:
+        return 2 * self.cap * self.S * self.S * 3
+
+    # ---- staging
+    def stage(self, rows, half: int) -> None:
+        import threading
+        if self._closed:
+            raise RuntimeError("RowStager is closed")
+        rows = np.ascontiguousarray(np.asarray(rows).reshape(-1), dtype=np.int64)
+        n = int(rows.shape[0])
+        assert 0 <= half <= 1 and 0 < n <= self.cap, (half, n, self.cap)
+        assert int(rows.min()) >= 0 and int(rows.max()) < self.images.shape[0], "dataset row out of range"
+        self.wait_issued(half)  # an earlier job of this half (an unused prefetch) is through
+        self.stages += 1
+        done, errors, lock = threading.Event(), [], threading.Lock()
+        parts = min(len(self._threads), max(1, n // 8))
+        left = [parts]
+        images, host, dev = self.images, self.host[half], self.dev
+        out = host.numpy()
+        copied, consumed, stream, device = self.copied[half], self.consumed[half], self.copy_stream, self.device
+
+        def part(lo, hi):
+            try:
+                if copied is not None:
+                    copied.synchronize()  # the copy that last read this pinned buffer is done
+                np.take(images, rows[lo:hi], axis=0, out=out[lo:hi], mode="clip")
+            except BaseException as e:  # noqa: BLE001 -- re-raised on the staging thread's caller (wait_issued)
+                errors.append(e)
+            with lock:
+                left[0] -= 1
+                last = left[0] == 0
+            if not last:
+                return
+            try:
+                if errors:
+                    return
+                if stream is None:
+                    dev[half, :n].copy_(host[:n])
+                    return
+                with torch.cuda.device(device), torch.cuda.stream(stream):
+                    stream.wait_event(consumed)  # the half's last reader is through
+                    dev[half, :n].copy_(host[:n], non_blocking=True)
+                    copied.record(stream)
+            except BaseException as e:  # noqa: BLE001
+                errors.append(e)
+            finally:
+                done.set()
+
+        self._issued[half] = (done, errors)
+        cut = [n * i // parts for i in range(parts + 1)]
+        for i in range(parts):
+            self._jobs.put(lambda lo=cut[i], hi=cut[i + 1]: part(lo, hi))
+
+    def wait_issued(self, half: int) -> None:
+        """Host wait until the half's last ``stage`` has gathered and issued its copy; re-raises its error."""
+        job = self._issued[half]
+        if job is None:
+            return
+        done, errors = job
+        done.wait()
+        self._issued[half] = None
+        if errors:
+            raise errors[0]
+
+    def drain(self) -> None:
+        for h in (0, 1):
+            self.wait_issued(h)
+
+    def wait_copied(self, half: int) -> None:
+        self.wait_issued(half)
+        if self.cuda:
+            torch.cuda.current_stream(self.device).wait_event(self.copied[half])
+
+    def mark_consumed(self, half: int) -> None:
+        if self.cuda:
+            self.consumed[half].record(torch.cuda.current_stream(self.device))
+
+    # ---- shutdown
+    def close(self) -> None:
+        """Join the gather threads (idempotent).  They are daemons as well: a stager that is never closed does not
+        keep the process alive."""
+        if self._closed:
+            return
+        self._closed = True
+        for _ in self._threads:
+            self._jobs.put(None)
+        for t in self._threads:
+            t.join()
+
+    def threads_alive(self) -> int:
+        return sum(t.is_alive() for t in self._threads)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001 -- interpreter shutdown
+            pass
+
+
+class HostFeed:
+    """Which staging half holds which rows: the plan-side protocol over a RowStager (or anything with its
+    ``ensure`` / ``stage`` / ``wait_copied`` / ``mark_consumed`` / ``cap`` / ``generation``).
+
+    A step calls ``half = begin(rows)`` before it enqueues its reader and ``end(announced)`` after.  The halves
+    alternate.  ``begin`` takes the other half as it is if the rows announced at the last ``end`` are exactly the rows
+    now requested (``hits``), and stages the requested rows into it now otherwise (``syncs``): an announcement is a
+    hint, and correctness never depends on it.  ``end`` marks the step's half consumed, then starts staging the
+    announced rows into the other half -- whose own consumed mark dates from the step before."""
+
+    def __init__(self, stager, prefetch: bool = True):
+        self.stager = stager
+        self.prefetch = prefetch  # False: every step is staged synchronously (measurements)
+        self.half = 1  # the half of the last step
+        self.ahead = None  # rows staged into the other half by the last end()
+        self._gen = stager.generation
+        self.hits = self.syncs = 0
+
+    def begin(self, rows) -> int:
+        st = self.stager
+        rows = np.asarray(rows, dtype=np.int64).reshape(-1)
+        if rows.shape[0] > st.cap:
+            st.ensure(rows.shape[0])
+        if st.generation != self._gen:
+            self._gen, self.ahead = st.generation, None  # reallocated halves hold nothing
+        half = 1 - self.half
+        if self.ahead is not None and np.array_equal(self.ahead, rows):
+            self.hits += 1
+        else:
+            st.stage(rows, half)
+            self.syncs += 1
+        self.ahead = None
+        st.wait_copied(half)
+        self.half = half
+        return half
+
+    def end(self, announced=None) -> None:
+        st = self.stager
+        st.mark_consumed(self.half)
+        if not self.prefetch or announced is None:
+            return
+        announced = np.array(announced, dtype=np.int64).reshape(-1)
+        if 0 < announced.shape[0] <= st.cap:
+            st.stage(announced, 1 - self.half)
+            self.ahead = announced
+
+
+class HostImageNetDataset(DeviceDataset):
+    """The ImageNet-style set with the training images on the host: ``train_x`` is the (memory-mapped) numpy array
+    [N, S, S, 3] uint8 and is never copied whole; the labels, the validation set and the evaluation cache live on the
+    device exactly as in DeviceDataset.  A step's rows reach the device through the set's RowStager (``feed``), and
+    the staged form of the input kernel reads them there (``ops.augment_imagenet_staged``): the same arithmetic and
+    the same draws as the resident set for the same rows, seed and counter."""
+
+    host_resident = True
+
+    def __init__(self, train_x, train_y, test_x, test_y, device, out_size, seed=0):
+        if not (isinstance(train_x, np.ndarray) and train_x.dtype == np.uint8 and train_x.ndim == 4
+                and train_x.shape[1] == train_x.shape[2] and train_x.shape[3] == 3 and out_size):
+            raise ValueError("HostImageNetDataset needs square uint8 [N, S, S, 3] numpy images and an out_size")
+        self.train_x = train_x
+        self._init_rest(train_y, test_x, test_y, device, augment_imagenet, eval_imagenet, seed, out_size)
+        self.imagenet = True
+        self.hip_augment = self.device.type == "cuda"
+        self._feed = None
+
+    @property
+    def feed(self) -> HostFeed:
+        if self._feed is None:
+            self._feed = HostFeed(RowStager(self.train_x, self.device))
+        return self._feed
+
+    def batch(self, idx, gen=None):
+        n, H = int(idx.numel()), self.out_size
+        seed, counter = self.next_rng()
+        rows = np.asarray(torch.as_tensor(idx).cpu(), dtype=np.int64).reshape(-1)
+        if not self.hip_augment:
+            x = augment_imagenet(torch.from_numpy(np.array(self.train_x[rows])), None, H, seed, counter)
+            return x, self.train_y[torch.from_numpy(rows)]
+        from .. import ops
+        feed = self.feed
+        half = feed.begin(rows)  # staged now: this path announces nothing
+        x = torch.empty(n, H, H, 3, dtype=torch.float32, device=self.device)
+        y = torch.empty(n, dtype=torch.int64, device=self.device)
+        rng = torch.tensor((seed, counter), dtype=torch.int32).to(self.device)
+        hw = torch.tensor([half], dtype=torch.int32).to(self.device)
+        ops.augment_imagenet_staged(feed.stager.dev, hw, self.train_y, torch.from_numpy(rows).to(self.device), rng, H,
+                                    True, out32=x, lab64=y)
+        feed.end(None)
+        return x, y
+
+    def close(self) -> None:
+        if self._feed is not None:
+            self._feed.stager.close()
 
 
 class SyntheticDataset:

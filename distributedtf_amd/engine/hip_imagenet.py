@@ -359,6 +359,8 @@ class HipImageNetBackend(HipBackend):
 
 
 class _ImageNetPlan(HipPlan):
+    host_src = False  # fed index batches of a host-resident set (datasets.HostImageNetDataset)
+
     def __init__(self, be: HipImageNetBackend, slots: List[int], sizes: List[int], eval_mode: bool = False,
                  src=None):
         self._init_members(be, slots, sizes, eval_mode)
@@ -375,6 +377,16 @@ class _ImageNetPlan(HipPlan):
             assert not eval_mode and src.out_size == H
             self.idx = torch.zeros(N, dtype=torch.long, device=dev)
             self.rng = torch.zeros(2, dtype=torch.int32, device=dev)
+            self.host_src = bool(getattr(src, "host_resident", False))
+            if self.host_src:
+                # a host-resident set: the step's rows are staged into one of two device halves (datasets.RowStager)
+                # and the input kernel reads them there; which half is a device word next to the rng, so the one
+                # captured graph serves both
+                words = torch.zeros(3, dtype=torch.int32, device=dev)
+                self.rng, self.half_word, self._words = words[:2], words[2:], words
+                self._idx_stage, self._announced = None, None
+                src.feed.stager.ensure(N)  # before the capture: the graph holds the staging tensor's address
+                self._stage_gen = src.feed.stager.generation
         H1 = H // 2
         H2 = (H1 + 1) // 2
         pool = {}
@@ -759,6 +771,8 @@ class _ImageNetPlan(HipPlan):
     def load_batch(self, batches, slots=None):
         if self.src is None:
             return super().load_batch(batches, slots)
+        if self.host_src:
+            return self._load_host_rows(batches)
         for s, b in zip(self.slots, batches):
             n, off = len(b), self.first[s]
             self.idx[off:off + n].copy_(b.idx, non_blocking=True)
@@ -766,12 +780,55 @@ class _ImageNetPlan(HipPlan):
             self._rng_stage = PinnedStager(2, torch.int32)
         self._rng_stage.upload(self.rng, self.src.next_rng())
 
+    def _load_host_rows(self, batches):
+        """Index batches of a host-resident set.  The half that holds this step's rows -- all members' rows
+        concatenated in plan order -- is the one prefetched during the last step if the rows announced then are the
+        rows requested now, else it is staged now; the compute stream waits for its "copied" event; rows, rng and the
+        half word go up through pinned stagers.  ``run`` records "consumed" and starts the next prefetch.  Event
+        waits and records stay outside the captured graph."""
+        import numpy as np
+        rows = np.empty(self.N, dtype=np.int64)
+        ahead = np.empty(self.N, dtype=np.int64)
+        announced = True
+        for s, b in zip(self.slots, batches):
+            n, off = len(b), self.first[s]
+            rows[off:off + n] = np.asarray(b.idx.cpu() if isinstance(b.idx, torch.Tensor) else b.idx).reshape(-1)
+            nxt = getattr(b, "next_rows", None)
+            if nxt is None or len(nxt) != n:
+                announced = False
+            else:
+                ahead[off:off + n] = np.asarray(nxt.cpu() if isinstance(nxt, torch.Tensor) else nxt).reshape(-1)
+        feed = self.src.feed
+        half = feed.begin(rows)
+        if feed.stager.generation != self._stage_gen:  # the halves were reallocated: the graph holds a dead address
+            self._stage_gen, self.graph = feed.stager.generation, None
+        if self._idx_stage is None:
+            self._idx_stage = PinnedStager(self.N, torch.int64)
+            self._rng_stage = PinnedStager(3, torch.int32)
+        self._idx_stage.upload_array(self.idx, torch.from_numpy(rows))
+        self._rng_stage.upload(self._words, tuple(self.src.next_rng()) + (half,))
+        self._announced = ahead if announced else None
+
+    def run(self):
+        if self.src is None or not self.host_src:
+            return super().run()
+        if self.graph is None:
+            self.src.feed.stager.drain()  # no gather thread talks to the device while the step is captured
+        super().run()
+        self.src.feed.end(self._announced)  # "consumed" after the replay is enqueued, then the next step's rows
+        self._announced = None
+
     def _marker_augment(self, _):
         """The "augment" marker of a plan fed index batches: dataset rows -> ``xin8`` (the stem's layout, s2d or
         padded) and ``labels`` in one launch inside the step graph; crops keyed per member (its step counter + the
         dataset row): placement-invariant (data.hip)."""
         e, src = self.e, self.src
         out = dict(out_s2d=self.xin8) if self.be.s2d else dict(out_pad=self.xin8)
+        if self.host_src:
+            ops.augment_imagenet_staged(src.feed.stager.dev, self.half_word, src.train_y, self.idx, self.rng, self.H,
+                                        True, lab32=self.labels,
+                                        member_keys=(self.img_slot, e.state, e.S, 3 * e.Pp + e.R), **out)
+            return
         ops.augment_imagenet(src.train_x, src.train_y, self.idx, self.rng, self.H, True, lab32=self.labels,
                              member_keys=(self.img_slot, e.state, e.S, 3 * e.Pp + e.R), **out)
 

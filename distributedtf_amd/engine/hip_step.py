@@ -72,6 +72,19 @@ class PinnedStager:
         dst.copy_(self.host[:len(values)], non_blocking=True)
         self.evt.record()
 
+    def upload_array(self, dst, src):
+        """``upload`` of a host tensor of ``dst``'s dtype and size, copied into the staging buffer in one piece."""
+        if dst.device.type != "cuda" or self.host is None:
+            dst.copy_(src)
+            return
+        if self.evt is None:
+            self.evt = torch.cuda.Event()
+        else:
+            self.evt.synchronize()
+        self.host[:src.numel()].copy_(src)
+        dst.copy_(self.host[:src.numel()], non_blocking=True)
+        self.evt.record()
+
 
 def note_step_advanced(e, slots):
     """Host mirror of ``advance_steps`` (call once per executed step)."""

@@ -159,6 +159,10 @@ class EngineModel(ModelBase):
     @classmethod
     def reset_engines(cls):
         EngineModel._engines.clear()
+        for ds in EngineModel._datasets.values():
+            close = getattr(ds, "close", None)  # a host-resident set joins its gather threads
+            if close is not None:
+                close()
         EngineModel._datasets.clear()
 
     def dataset(self):
@@ -268,13 +272,26 @@ class EngineModel(ModelBase):
         gen = self._data_gen(ds, gen)
         if not hasattr(self, "_perm") or self._perm_pos + b > self._perm.numel():
             self._perm_gen_state = gen.get_state() if gen is not None else None  # (stream_state: exact resume)
-            self._perm = torch.randperm(ds.num_train, device=ds.train_x.device, generator=gen)
+            self._perm = torch.randperm(ds.num_train, device=self._perm_device(ds), generator=gen)
             self._perm_pos = 0
         idx = self._perm[self._perm_pos:self._perm_pos + b]
         self._perm_pos += b
         if getattr(ds, "hip_augment", False):
+            if getattr(ds, "host_resident", False):
+                # the rows of the member's next batch, announced so that the plan can stage them while this step
+                # runs; nothing at an epoch end (the next permutation is not drawn yet).  A hint only: the plan
+                # compares it with what is requested next (a batch size moved by explore, an exploit, a resume)
+                end = self._perm_pos + b
+                nxt = self._perm[self._perm_pos:end] if end <= self._perm.numel() else None
+                return datasets.IndexBatch(ds, idx, next_rows=nxt)
             return datasets.IndexBatch(ds, idx)
         return ds.batch(idx, gen)
+
+    @staticmethod
+    def _perm_device(ds):
+        """Where a member's epoch permutation is drawn: on the device next to a device-resident set; on the CPU for
+        a host-resident one, whose rows are gathered by the host -- no device-to-host copy enters the step loop."""
+        return "cpu" if getattr(ds, "host_resident", False) else ds.train_x.device
 
     def stream_state(self):
         """Explore rng + the member's data stream (its generator state when the current epoch permutation was drawn,
@@ -310,7 +327,7 @@ class EngineModel(ModelBase):
         st = lambda h: torch.frombuffer(bytearray(bytes.fromhex(h)), dtype=torch.uint8)  # noqa: E731
         g.set_state(st(data["perm_gen"]))
         self._perm_gen_state = g.get_state()
-        self._perm = torch.randperm(ds.num_train, device=ds.train_x.device, generator=g)
+        self._perm = torch.randperm(ds.num_train, device=self._perm_device(ds), generator=g)
         self._perm_pos = int(data["perm_pos"])
         g.set_state(st(data["gen"]))
 
@@ -319,11 +336,13 @@ class EngineModel(ModelBase):
         batches do not depend on which members share its rank or plan, so a PBT run reads the same data at any
         placement of the population (tests/test_gpu_placement.py).  Replicas of a data-parallel group draw
         different shards."""
-        if ds.device.type != "cuda":
+        host = getattr(ds, "host_resident", False)  # its permutation is drawn on the CPU, wherever the set's device
+        if ds.device.type != "cuda" and not host:
             return shared
         g = getattr(self, "_gen", None)
-        if g is None or g.device != ds.device:
-            g = torch.Generator(device=ds.device)
+        dev = torch.device("cpu") if host else ds.device
+        if g is None or g.device != dev:
+            g = torch.Generator(device=dev)
             g.manual_seed(int(self.rng.random() * 1e9) + (7919 * self.dp.rank if self.dp else 0))
             self._gen = g
         return g

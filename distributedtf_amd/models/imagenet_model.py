@@ -12,6 +12,8 @@ Data: pre-decoded uint8 arrays under ``data_dir`` (``datasets.load_imagenet_arra
 ``val_labels.npy``) resident on the device, cropped / resampled / flipped by the
 HIP input kernel inside the step graph (data.hip); ``use_synthetic_data="learnable"``
 is a class-template set through the same path; otherwise a fixed synthetic batch.
+``imagenet_data="host"`` keeps the training images on the host instead and stages
+every step's rows (``datasets.HostImageNetDataset``).
 """
 
 from __future__ import annotations
@@ -39,8 +41,11 @@ def _upload(arr, device, dtype, rows=1024):
 
 class ImageNetModel(Cifar10Model):
     def __init__(self, cluster_id, hparams, save_base_dir, seed=None, resnet_size=50, image_size=224,
-                 num_classes=None, data_dir=None, use_synthetic_data=None, **kw):
+                 num_classes=None, data_dir=None, use_synthetic_data=None, imagenet_data="device", **kw):
         self.image_size = int(image_size)
+        if imagenet_data not in ("device", "host"):
+            raise ValueError("imagenet_data must be device or host, not %r" % (imagenet_data,))
+        self.imagenet_data = imagenet_data  # --imagenet_data: where the training images live
         if self.image_size < 32 or self.image_size % 32:
             raise ValueError("image_size must be a positive multiple of 32, not %d" % self.image_size)
         self._real = use_synthetic_data in (None, False) and datasets.imagenet_arrays_available(data_dir)
@@ -61,12 +66,24 @@ class ImageNetModel(Cifar10Model):
     def make_dataset(self, device):
         H = self.image_size
         kw = dict(augment=datasets.augment_imagenet, eval_transform=datasets.eval_imagenet, out_size=H)
+        host = self.imagenet_data == "host"
+        if host and not (self._real or self._learnable):
+            raise ValueError("imagenet_data=host needs the ImageNet arrays under data_dir or "
+                             "use_synthetic_data='learnable'")
         if self._real:
-            trx, tr_y, vax, va_y = datasets.load_imagenet_arrays(self.data_dir, device, out_size=H)
+            # staging is sized by the largest step: every slot of the engine at the largest batch size explore allows
+            # (256), or this member's if --batch_size pins a larger one
+            rows = self.engine.capacity * max(256, int(self.hparams["batch_size"]))
+            trx, tr_y, vax, va_y = datasets.load_imagenet_arrays(self.data_dir, device, out_size=H, resident=not host,
+                                                                 stage_rows=rows)
             hi = max(int(tr_y.max()), int(va_y.max()))
             if int(tr_y.min()) < 0 or hi >= self.num_classes:
                 raise ValueError("%s: labels span 0..%d but the model has %d classes"
                                  % (self.data_dir, hi, self.num_classes))
+            if host:  # the training images stay in the memory-mapped file; everything else as the resident set
+                return datasets.HostImageNetDataset(trx, np.array(tr_y, dtype=np.int64),
+                                                    _upload(vax, device, torch.uint8),
+                                                    np.array(va_y, dtype=np.int64), device, out_size=H)
             return datasets.DeviceDataset(_upload(trx, device, torch.uint8), np.array(tr_y, dtype=np.int64),
                                           _upload(vax, device, torch.uint8), np.array(va_y, dtype=np.int64),
                                           device, **kw)
@@ -78,13 +95,15 @@ class ImageNetModel(Cifar10Model):
             trx, tr_y, tex, te_y = datasets.learnable_imagenet(n_train=8000 if on_gpu else 256,
                                                                n_test=1000 if on_gpu else 64, side=side,
                                                                num_classes=min(self.num_classes, LEARNABLE_NUM_CLASSES))
+            if host:  # the same set, kept as a numpy array on the host
+                return datasets.HostImageNetDataset(trx, tr_y, tex, te_y, device, out_size=H)
             return datasets.DeviceDataset(trx, tr_y, tex, te_y, device, **kw)
         return datasets.SyntheticDataset((H, H, 3), self.num_classes, device, max_batch=256, n_eval=256)
 
     def dataset(self):
         """One dataset per (device, source, input size, classes): members of one population share it."""
         key = (type(self).__name__, str(self.device), self.data_dir, self.use_synthetic_data, self.image_size,
-               self.num_classes)
+               self.num_classes) + (("host",) if self.imagenet_data == "host" else ())
         ds = Cifar10Model._datasets.get(key)
         if ds is None:
             ds = Cifar10Model._datasets[key] = self.make_dataset(self.device)

@@ -296,6 +296,25 @@ register("dtf_augment_imagenet", [c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                                   c_void_p])
 
 
+def _imagenet_launch_checks(S, H, n, labels, idx, rng, out_s2d, out_pad, out32, lab32, lab64, boxes, member_keys):
+    """The argument checks both forms of the ImageNet input kernel share: sizes, the index / label / rng tensors, every
+    output that is given, the member keys.  Returns the keys as (slot, state, stride, column)."""
+    assert H >= 2 and H % 2 == 0 and H <= 1024 and (2 * H + 1) * S < 2 ** 23, "output size: even, (2H+1) S < 2^23"
+    assert labels.dtype == torch.int64 and labels.dim() == 1 and idx.dtype == torch.int64
+    assert idx.is_contiguous() and rng.numel() >= 2 and rng.dtype == torch.int32
+    for t, shp, dt in ((out_s2d, (H // 2, H // 2, 16), act_dtype()), (out_pad, (H, H, 8), act_dtype()),
+                       (out32, (H, H, 3), torch.float32)):
+        if t is not None:
+            assert t.dtype == dt and t.shape[0] >= n and tuple(t.shape[1:]) == shp and t.is_contiguous()
+    for t, dt, per in ((lab32, torch.int32, 1), (lab64, torch.int64, 1), (boxes, torch.int32, 5)):
+        if t is not None:
+            assert t.dtype == dt and t.numel() >= n * per and t.is_contiguous()
+    ks, kst, kstride, kcol = member_keys if member_keys is not None else (None, None, 0, 0)
+    if ks is not None:
+        assert ks.dtype == torch.int32 and ks.numel() >= n and kst.dtype == torch.float32
+    return ks, kst, kstride, kcol
+
+
 def augment_imagenet(images, labels, idx, rng, out_size, augment=True, out_s2d=None, out_pad=None, out32=None,
                      lab32=None, lab64=None, boxes=None, member_keys=None):
     """Fused gather + random-resized crop (``augment``; else the central crop of side round(0.875 S)) + bilinear
@@ -310,21 +329,40 @@ def augment_imagenet(images, labels, idx, rng, out_size, augment=True, out_s2d=N
     assert images.dtype == torch.uint8 and images.dim() == 4 and images.shape[3] == 3 and images.is_contiguous()
     S = int(images.shape[1])
     assert images.shape[2] == S and 1 <= S <= 4096, "square stored images up to 4096"
-    assert H >= 2 and H % 2 == 0 and H <= 1024 and (2 * H + 1) * S < 2 ** 23, "output size: even, (2H+1) S < 2^23"
-    assert labels.dtype == torch.int64 and labels.numel() == images.shape[0] and idx.dtype == torch.int64
-    assert idx.is_contiguous() and rng.numel() >= 2 and rng.dtype == torch.int32
+    assert labels.numel() == images.shape[0]
     n = int(idx.numel())
-    for t, shp, dt in ((out_s2d, (H // 2, H // 2, 16), act_dtype()), (out_pad, (H, H, 8), act_dtype()),
-                       (out32, (H, H, 3), torch.float32)):
-        if t is not None:
-            assert t.dtype == dt and t.shape[0] >= n and tuple(t.shape[1:]) == shp and t.is_contiguous()
-    for t, dt, per in ((lab32, torch.int32, 1), (lab64, torch.int64, 1), (boxes, torch.int32, 5)):
-        if t is not None:
-            assert t.dtype == dt and t.numel() >= n * per and t.is_contiguous()
-    ks, kst, kstride, kcol = member_keys if member_keys is not None else (None, None, 0, 0)
-    if ks is not None:
-        assert ks.dtype == torch.int32 and ks.numel() >= n and kst.dtype == torch.float32
+    ks, kst, kstride, kcol = _imagenet_launch_checks(S, H, n, labels, idx, rng, out_s2d, out_pad, out32, lab32, lab64,
+                                                     boxes, member_keys)
     check(lib().dtf_augment_imagenet(ptr(images), ptr(labels), ptr(idx), ptr(rng), n, int(images.shape[0]), S, H,
                                      1 if augment else 0, ptr(out_s2d), ptr(out_pad), ptr(out32), ptr(lab32),
                                      ptr(lab64), ptr(boxes), ptr(ks), ptr(kst), int(kstride), int(kcol), stream()),
           "augment_imagenet")
+
+
+register("dtf_augment_imagenet_staged", [c_void_p, c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_int, c_long, c_int,
+                                         c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                         c_void_p, c_void_p, c_long, c_long, c_void_p])
+
+
+def augment_imagenet_staged(stage, half, labels, idx, rng, out_size, augment=True, out_s2d=None, out_pad=None,
+                            out32=None, lab32=None, lab64=None, boxes=None, member_keys=None):
+    """:func:`augment_imagenet` for a set whose pixels live on the host: image ``p`` of the launch is read from
+    ``stage[half][p]`` -- stage [2, cap, S, S, 3] uint8, the rows copied there before the launch; ``half`` a one-word
+    int32 device tensor (0 or 1), read on the device, so one captured graph serves both halves.  ``idx`` [n] are still
+    the dataset rows: they key the crop / flip draw and select the label from ``labels`` [N] (device), never a pixel.
+    Outputs and ``member_keys`` as for the resident form, bit for bit; ``n > cap`` fails the launcher's argument
+    check (hipErrorInvalidValue, no launch)."""
+    H = int(out_size)
+    assert stage.dtype == torch.uint8 and stage.dim() == 5 and stage.shape[0] == 2 and stage.shape[4] == 3
+    assert stage.is_contiguous() and stage.is_cuda
+    cap, S = int(stage.shape[1]), int(stage.shape[2])
+    assert stage.shape[3] == S and 1 <= S <= 4096, "square stored images up to 4096"
+    assert half.dtype == torch.int32 and half.numel() == 1 and half.device == stage.device
+    n = int(idx.numel())
+    ks, kst, kstride, kcol = _imagenet_launch_checks(S, H, n, labels, idx, rng, out_s2d, out_pad, out32, lab32, lab64,
+                                                     boxes, member_keys)
+    check(lib().dtf_augment_imagenet_staged(ptr(stage), ptr(half), cap, ptr(labels), ptr(idx), ptr(rng), n,
+                                            int(labels.numel()), S, H, 1 if augment else 0, ptr(out_s2d),
+                                            ptr(out_pad), ptr(out32), ptr(lab32), ptr(lab64), ptr(boxes), ptr(ks),
+                                            ptr(kst), int(kstride), int(kcol), stream()),
+          "augment_imagenet_staged")

@@ -146,8 +146,15 @@ __device__ __forceinline__ uint32_t isqrt32(uint32_t v) {  // floor(sqrt(v)), v 
   return r;
 }
 
+// One body, two entry points.  STAGED = false (dtf_augment_imagenet): image p of the launch is images[idx[p]], the
+// set lives on the device.  STAGED = true (dtf_augment_imagenet_staged): the set's pixels live on the host and image p
+// was copied to stage[half][p] of a two-half staging tensor [2][cap][S][S][3] before the launch; half (0 or 1) is read
+// from a one-word device tensor -- one more wave-uniform scalar load, no more loads per pixel --, so one captured
+// graph serves both halves.  idx[p] is still the dataset row: it keys the draw and selects the label, never a pixel.
+template <bool STAGED>
 __global__ __launch_bounds__(256) void augment_imagenet_kernel(
-    const uint8_t* __restrict__ images, const long* __restrict__ labels_src, const long* __restrict__ idx,
+    const uint8_t* __restrict__ images, const int* __restrict__ half_word, long cap,
+    const long* __restrict__ labels_src, const long* __restrict__ idx,
     const uint32_t* __restrict__ rng, int n, long nrows, int S, int H, int augment, bf16_t* __restrict__ out_s2d,
     bf16_t* __restrict__ out_pad, float* __restrict__ out32, int* __restrict__ lab32, long* __restrict__ lab64,
     int* __restrict__ boxes, const int* __restrict__ key_slot, const float* __restrict__ key_state, long key_stride,
@@ -227,7 +234,9 @@ __global__ __launch_bounds__(256) void augment_imagenet_kernel(
     tx[d][0] = x0 + ix;
     tx[d][1] = x0 + min(ix + 1, bw - 1);
   }
-  const uint8_t* im = images + src * ((long)S * S * CH);
+  // staged: the launch's image p of the half named by the device word (masked: a bad word cannot leave the tensor)
+  const long img = STAGED ? (long)(half_word[0] & 1) * cap + p : src;
+  const uint8_t* im = images + img * ((long)S * S * CH);
   const float mean[CH] = {123.68f, 116.78f, 103.94f};
   float v[2][2][CH];
 #pragma unroll
@@ -273,8 +282,10 @@ __global__ __launch_bounds__(256) void augment_imagenet_kernel(
 
 // Host-side argument check of dtf_augment_imagenet: the sizes at which the kernel's integer positions stay exact in
 // fp32 ((2 o + 1) * crop < 2^23) and its int offsets cannot overflow.
-static bool imagenet_args_ok(int n, long nrows, int S, int H) {
+// cap >= 0: the staged form's images per staging half, which must hold the launch (n <= cap).
+static bool imagenet_args_ok(int n, long nrows, int S, int H, long cap = -1) {
   if (n < 0 || nrows < 1 || S < 1 || S > 4096 || H < 2 || (H & 1) || H > 1024) return false;
+  if (cap >= 0 && (n > cap || cap < 1)) return false;
   if ((long)(2 * H + 1) * S >= (1L << 23)) return false;
   const long cpi = ((long)(H / 2) * (H / 2) + 63) / 64;
   return (long)n * cpi < (1L << 31) - 4;
@@ -287,9 +298,25 @@ DTF_API int dtf_augment_imagenet(const uint8_t* images, const long* labels_src, 
   if (!imagenet_args_ok(n, nrows, S, H)) return (int)hipErrorInvalidValue;
   if (n == 0) return 0;
   const long cpi = ((long)(H / 2) * (H / 2) + 63) / 64;
-  hipLaunchKernelGGL(augment_imagenet_kernel, dim3((unsigned)((n * cpi + 3) / 4)), dim3(256), 0, stream, images,
-                     labels_src, idx, rng, n, nrows, S, H, augment, out_s2d, out_pad, out32, lab32, lab64, boxes,
-                     key_slot, key_state, key_stride, key_col);
+  hipLaunchKernelGGL(augment_imagenet_kernel<false>, dim3((unsigned)((n * cpi + 3) / 4)), dim3(256), 0, stream, images,
+                     (const int*)nullptr, 0L, labels_src, idx, rng, n, nrows, S, H, augment, out_s2d, out_pad, out32,
+                     lab32, lab64, boxes, key_slot, key_state, key_stride, key_col);
+  return DTF_CHECK_LAUNCH();
+}
+
+// The staged form (augment_imagenet_kernel<true>): stage [2][cap][S][S][3] uint8, half_word one int32 on the device
+// (0 or 1); nrows is the dataset's row count (labels_src, the clamp of idx).  n images need n <= cap.
+DTF_API int dtf_augment_imagenet_staged(const uint8_t* stage, const int* half_word, long cap, const long* labels_src,
+                                        const long* idx, const uint32_t* rng, int n, long nrows, int S, int H,
+                                        int augment, bf16_t* out_s2d, bf16_t* out_pad, float* out32, int* lab32,
+                                        long* lab64, int* boxes, const int* key_slot, const float* key_state,
+                                        long key_stride, long key_col, hipStream_t stream) {
+  if (!imagenet_args_ok(n, nrows, S, H, cap)) return (int)hipErrorInvalidValue;
+  if (n == 0) return 0;
+  const long cpi = ((long)(H / 2) * (H / 2) + 63) / 64;
+  hipLaunchKernelGGL(augment_imagenet_kernel<true>, dim3((unsigned)((n * cpi + 3) / 4)), dim3(256), 0, stream, stage,
+                     half_word, cap, labels_src, idx, rng, n, nrows, S, H, augment, out_s2d, out_pad, out32, lab32,
+                     lab64, boxes, key_slot, key_state, key_stride, key_col);
   return DTF_CHECK_LAUNCH();
 }
 

@@ -141,6 +141,11 @@ def build_parser(defaults: Optional[Dict[str, Any]] = None) -> argparse.Argument
     p.add_argument("--image_size", type=int, default=None,
                    help="imagenet: the model's input side (default 224; a multiple of 32): real and learnable images "
                         "are cropped and resampled to it")
+    p.add_argument("--imagenet_data", default="device", choices=["device", "host"],
+                   help="imagenet: where the training images live. device (default): the whole uint8 set on the GPU. "
+                        "host: train_images.npy stays memory mapped on the host and every step's rows are staged "
+                        "into one of two device buffers while the step before runs (sets larger than device memory); "
+                        "needs the arrays under --data_dir or --use_synthetic_data learnable")
     p.add_argument("--max_train_steps", type=int, default=None)
     p.add_argument("--debug_steps", type=int, default=None, help="MNIST: steps per 'epoch' (reference used 10)")
     p.add_argument("--batch_size", type=int, default=None, help="override every member's batch_size")
@@ -222,6 +227,8 @@ class MainArgs(argparse.Namespace):
             kw["resnet_version"] = self.resnet_version
         if self.model == "imagenet" and getattr(self, "image_size", None):
             kw["image_size"] = self.image_size
+        if self.model == "imagenet" and getattr(self, "imagenet_data", "device") == "host":
+            kw["imagenet_data"] = "host"
         if self.model == "mnist" and self.debug_steps:
             kw["debug_steps"] = self.debug_steps
         if self.model == "mnist":
@@ -340,6 +347,14 @@ def parse_main_args(argv=None, defaults=None) -> MainArgs:
     if args.deterministic and args.backend == "hip" and args.model != "toy" and not hip_deterministic(args):
         p.error("--deterministic with --backend hip: the %s HIP step has no deterministic build yet; use --backend "
                 "auto (deterministic PyTorch algorithms) or torch" % args.model)
+    if args.imagenet_data == "host":
+        from ..data.datasets import imagenet_arrays_available
+        if args.model != "imagenet":
+            p.error("--imagenet_data host needs --model imagenet, not %s" % args.model)
+        if args.use_synthetic_data != "learnable" and not (args.use_synthetic_data in (None, False)
+                                                           and imagenet_arrays_available(args.data_dir)):
+            p.error("--imagenet_data host needs the ImageNet arrays under --data_dir or --use_synthetic_data "
+                    "learnable (the fixed synthetic batch has no rows to stage)")
     if args.epochs_between_evals < 1:
         p.error("--epochs_between_evals must be >= 1")
     if args.deterministic and args.debug_kernels:

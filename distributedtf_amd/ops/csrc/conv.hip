@@ -2569,6 +2569,14 @@ DTF_API int dtf_conv_dgrad(const ConvArgs* args, int cin, int cout, int s, int k
 
 DTF_API int dtf_conv_bwd_fused(const ConvArgs* args, int c, int mode_dy, int epi, int nblocks, int lds,
                                hipStream_t stream) {
+  if (nblocks <= 0) return 0;
+  // a zeroed ConvArgs would send every workgroup into trailing_reduce with r_nblk = 0
+  DTF_HOST_CHECK(args->n_main > 0 && nblocks >= args->n_main && args->rows == 8);
+  if (nblocks > args->n_main) {  // trailing workgroups: the previous launch's dW slab reduction
+    DTF_HOST_CHECK(args->rslab != nullptr && args->rtab != nullptr && args->grads != nullptr);
+    DTF_HOST_CHECK(args->r_c == 16 || args->r_c == 32 || args->r_c == 64);
+    DTF_HOST_CHECK(args->r_nblk > 0 && (nblocks - args->n_main) % args->r_nblk == 0);
+  }
   FUSED_CASE(16, 0, 0)  // conv_b: dy = residual grad, x = h (BN2)
   FUSED_CASE(32, 0, 0)
   FUSED_CASE(64, 0, 0)

@@ -1,11 +1,13 @@
-"""Constructions for the exact tests of the deferred CIFAR backward kernels of ops/csrc/conv.hip: the dgrad role
+"""Constructions for the exact tests of the stride-1 CIFAR backward kernels of ops/csrc/conv.hip: the dgrad role
 ``dtf_conv_bwd_dg`` (13 instantiations), the deferred weight-gradient launch ``dtf_conv_wgrad_all`` with its dW slabs,
-and the slab reductions ``dtf_slab_reduce_all`` / ``dtf_dw_slab_reduce``.  Operands, float64 references, exactness
-conditions and buffer layouts, all without a device; the population layout, the work lists, the guarded buffers and
-the BN+ReLU snap construction are those of tests/_conv_exact.py.  Used by tests/test_gpu_conv_bwd_dg.py,
-tests/test_gpu_conv_wgrad_deferred.py and, for the conditions themselves, tests/test_conv_bwd_exact_constructions.py.
-(``dtf_conv_bwd_fused``, ``dtf_conv_dgrad``, ``dtf_conv_wgrad`` and ``dtf_conv_trans_multi`` are not covered; the
-cases here are keyed by (C, mode, epi, rows) so that further roles can be added beside them.)
+the slab reductions ``dtf_slab_reduce_all`` / ``dtf_dw_slab_reduce``, and the fused launch ``dtf_conv_bwd_fused`` (16
+instantiations: both roles over shared tiles, plus its trailing slab-reduction workgroups).  Operands, float64
+references, exactness conditions and buffer layouts, all without a device; the population layout, the work lists, the
+guarded buffers and the BN+ReLU snap construction are those of tests/_conv_exact.py.  Used by
+tests/test_gpu_conv_bwd_dg.py, tests/test_gpu_conv_wgrad_deferred.py, tests/test_gpu_conv_bwd_fused.py and, for the
+conditions themselves, tests/test_conv_bwd_exact_constructions.py.  (``dtf_conv_dgrad``, ``dtf_conv_wgrad`` and
+``dtf_conv_trans_multi`` are not covered; the cases here are keyed by (C, mode, epi, rows) so that further roles can
+be added beside them.)
 
 Geometry.  The kernels' compile-time ones: H = W = 512 / C at C = 16, 32, 64, bands of 8 rows (4: half-image bands of
 the dgrad role at C = 64).
@@ -61,7 +63,17 @@ The jobs of a launch are interleaved by its ``map`` instead.
 
 Slab layout.  A slab is [j][m][t][r] (NJ = ceil(NTN / 4) x MT = C / 16 x 256 threads x 4): tile nt = t / 64 + 4 j of
 the NTN = 9 C / 16 (tap, ci) tiles, (tap, ci) = (16 nt / C, 16 nt % C + t % 16), co = 16 m + 4 (t % 64 / 16) + r; tiles
-nt >= NTN (C = 16 and C = 32 have them) are duplicates that a reduction must skip (``slab_map``)."""
+nt >= NTN (C = 16 and C = 32 have them) are duplicates that a reduction must skip (``slab_map``).
+
+Fused launch (ROLE 0).  ``fused_case`` is ONE operand set for both halves: the dgrad half above (unit 1 or 0.5) and
+the wgrad half above (unit 0.5 or 0.25) from the same dY and the same x, over a work list grouped by member with its
+slab reduce table; ``check_fused`` asserts both halves' conditions on it.  EPI & 2 (v1, identity BN): x is a small
+integer tensor with negatives and zeros, the X tile relu(x) and the mask x > 0 -- what the kernel computes with scale
+1, shift 0; without EPI & 8 no statistics are written and the epilogue's statistics pointer is NULL, its gamma / beta
+columns NaN.  EPI & 8 (v1 chain): x3 is the input of the chained BN (``c.chain``: the forward construction's dyadic
+x, its unevenly split statistics, one negative-variance channel per member), row 0 of ``st_out`` gets sum(dz), row 1
+sum(dz (x3 inv - mean inv)).  ``trail_case``: hand-written slabs of ANOTHER conv of width r_c that the trailing
+workgroups of a launch (blockIdx >= n_main) add into the gradient row at r_goff."""
 import functools
 
 import torch
@@ -284,9 +296,9 @@ def check_dy(c):
     assert bool(torch.isnan(c.dgamma[c.idle]).all())
 
 
-def check_mask_bn(c):
-    """The forward snap conditions of kx.check_case on the BN of the layer input."""
-    e = c.ep
+def check_mask_bn(c, e=None):
+    """The forward snap conditions of kx.check_case on the BN of the layer input (or on BN operands ``e``)."""
+    e = c.ep if e is None else e
     v, sn = e.v, e.snap
     for dt in (torch.bfloat16, torch.float16):
         assert torch.equal(e.x.to(dt).double(), e.x)
@@ -322,9 +334,44 @@ def check_work(c, grouped):
 def param_rows(c):
     rows = torch.full((CAP, kx.P_MSTRIDE), NAN, dtype=torch.float64)
     rows[:, IN_GAMMA:IN_GAMMA + c.C] = c.dgamma
-    rows[:, EP_GAMMA:EP_GAMMA + c.C] = c.ep.gamma
-    rows[:, EP_BETA:EP_BETA + c.C] = c.ep.beta
+    bn = c.chain or c.ep  # EPI bit 8: the epilogue columns are the chained BN's
+    rows[:, EP_GAMMA:EP_GAMMA + c.C] = bn.gamma
+    rows[:, EP_BETA:EP_BETA + c.C] = bn.beta
     return rows
+
+
+def _dgrad_ref(c):
+    """c.y = mask ? conv^T(c.dy) [+ res] : 0 with the summed magnitudes c.absy, and the sum(y) row c.st / c.st_abs."""
+    cc = c.C
+    shape = (c.n_img, c.H, c.H, cc)
+    c.y, c.absy = torch.empty(shape, dtype=torch.float64), torch.empty(shape, dtype=torch.float64)
+    c.st = torch.zeros(CAP, 64, dtype=torch.float64)
+    c.st_abs = torch.zeros(CAP, 64, dtype=torch.float64)
+    for sl, f, e in ranges(c.slots, c.sizes):
+        wt = c.w[sl].permute(3, 0, 1, 2).contiguous()  # conv_transpose2d weight [Co][Ci][ky][kx]
+        dyn = c.dy[f:e].permute(0, 3, 1, 2).contiguous()
+        dx = F.conv_transpose2d(dyn, wt, padding=1).permute(0, 2, 3, 1)
+        ab = F.conv_transpose2d(dyn.abs(), wt.abs(), padding=1).permute(0, 2, 3, 1)
+        if c.epi & 1:
+            dx, ab = dx + c.res[f:e], ab + c.res[f:e].abs()
+        c.absy[f:e] = ab
+        c.y[f:e] = torch.where(c.ep.snap[f:e] > 0, dx, torch.zeros_like(dx))
+        c.st[sl, :cc] = c.y[f:e].sum((0, 1, 2))
+        c.st_abs[sl, :cc] = c.y[f:e].abs().sum((0, 1, 2))
+
+
+def _dw_ref(c):
+    """c.dw [slot][co][ky][kx][ci] = sum over pixels of c.dy[p][co] c.ep.xin[p + (ky - 1, kx - 1)][ci], and c.absdw."""
+    cc, hh = c.C, c.H
+    c.dw = torch.zeros(CAP, cc, 3, 3, cc, dtype=torch.float64)
+    c.absdw = torch.zeros_like(c.dw)
+    xp = F.pad(c.ep.xin, (0, 0, 1, 1, 1, 1))
+    for sl, f, e in ranges(c.slots, c.sizes):
+        for ky in range(3):
+            for kx_ in range(3):
+                xs = xp[f:e, ky:ky + hh, kx_:kx_ + hh]
+                c.dw[sl, :, ky, kx_] = torch.einsum("nhwo,nhwi->oi", c.dy[f:e], xs)
+                c.absdw[sl, :, ky, kx_] = torch.einsum("nhwo,nhwi->oi", c.dy[f:e].abs(), xs.abs())
 
 
 # ------------------------------------------------------------------------------------------- the dgrad role
@@ -340,7 +387,7 @@ DG_UNTESTED = []  # instantiations whose construction cannot meet its conditions
 def dg_case(cc, mode, epi, rows, uniform=False, nrep=8):
     c = Case()
     _geo(c, cc, rows, uniform, nrep)
-    c.mode, c.epi = mode, epi
+    c.mode, c.epi, c.chain = mode, epi, None
     seed = (cc * 131 + mode * 17 + epi * 5 + rows) * 1009 + uniform * 7919 + 424247
     c.ep = _mask_bn(c, seed)
     if mode == 0:
@@ -350,21 +397,7 @@ def dg_case(cc, mode, epi, rows, uniform=False, nrep=8):
     c.unit = 1.0 if mode == 0 else 0.5
     c.w = kx._weights(c, seed, 12 if mode == 0 else 10)  # IHWO: [CAP][Ci][3][3][Co]
     c.res = hints((c.n_img, c.H, c.H, cc), -8, 8, seed + 3) if epi & 1 else None
-    shape = (c.n_img, c.H, c.H, cc)
-    c.y, c.absy = torch.empty(shape, dtype=torch.float64), torch.empty(shape, dtype=torch.float64)
-    c.st = torch.zeros(CAP, 64, dtype=torch.float64)
-    c.st_abs = torch.zeros(CAP, 64, dtype=torch.float64)
-    for sl, f, e in ranges(c.slots, c.sizes):
-        wt = c.w[sl].permute(3, 0, 1, 2).contiguous()  # conv_transpose2d weight [Co][Ci][ky][kx]
-        dyn = c.dy[f:e].permute(0, 3, 1, 2).contiguous()
-        dx = F.conv_transpose2d(dyn, wt, padding=1).permute(0, 2, 3, 1)
-        ab = F.conv_transpose2d(dyn.abs(), wt.abs(), padding=1).permute(0, 2, 3, 1)
-        if epi & 1:
-            dx, ab = dx + c.res[f:e], ab + c.res[f:e].abs()
-        c.absy[f:e] = ab
-        c.y[f:e] = torch.where(c.ep.snap[f:e] > 0, dx, torch.zeros_like(dx))
-        c.st[sl, :cc] = c.y[f:e].sum((0, 1, 2))
-        c.st_abs[sl, :cc] = c.y[f:e].abs().sum((0, 1, 2))
+    _dgrad_ref(c)
     c.w[c.idle] = NAN
     c.st_seed = 1.0 + hints((CAP, nrep, 2, 64), 0, 4, seed + 4)
     _work(c, grouped=False)
@@ -437,7 +470,7 @@ WG_SETS = {0: [(64, 0), (32, 2), (64, 2), (32, 0)], 1: [(16, 2), (16, 0)]}  # cs
 def wg_job(cc, mode, uniform=False, nrep=8):
     c = Case()
     _geo(c, cc, 8, uniform, nrep)
-    c.mode, c.epi = mode, 0
+    c.mode, c.epi, c.chain = mode, 0, None
     seed = (cc * 137 + mode * 19) * 1013 + uniform * 7919 + 990001
     c.ep = _mask_bn(c, seed)
     if mode == 0:
@@ -445,16 +478,7 @@ def wg_job(cc, mode, uniform=False, nrep=8):
     else:
         _bn_bwd_input(c, seed, False)
     c.unit = 0.5 if mode == 0 else 0.25
-    hh = c.H
-    c.dw = torch.zeros(CAP, cc, 3, 3, cc, dtype=torch.float64)  # [slot][co][ky][kx][ci]
-    c.absdw = torch.zeros_like(c.dw)
-    xp = F.pad(c.ep.xin, (0, 0, 1, 1, 1, 1))
-    for sl, f, e in ranges(c.slots, c.sizes):
-        for ky in range(3):
-            for kx_ in range(3):
-                xs = xp[f:e, ky:ky + hh, kx_:kx_ + hh]
-                c.dw[sl, :, ky, kx_] = torch.einsum("nhwo,nhwi->oi", c.dy[f:e], xs)
-                c.absdw[sl, :, ky, kx_] = torch.einsum("nhwo,nhwi->oi", c.dy[f:e].abs(), xs.abs())
+    _dw_ref(c)
     _work(c, grouped=True)
     c.red = [[m * c.u[0], c.u[0], 0, m] for m in c.slots] if uniform else red_table(c.items)
     return c
@@ -594,3 +618,212 @@ def check_reduce_case(k):
     if not k.full:
         assert k.mag.max() < EXACT and bool((k.want == k.want.round()).all())
     assert bool((k.seed != 0).all())
+
+
+# ---------------------------------------------------------------------------------- the fused launch (ROLE 0)
+# every instantiation of dtf_conv_bwd_fused: (C, MODE_DY, EPI)
+FUSED_CASES = ([(cc, 0, 0) for cc in WIDTHS] + [(cc, 3, 0) for cc in WIDTHS] + [(cc, 2, 0) for cc in WIDTHS]
+               + [(16, 2, 1)] + [(cc, 2, 3) for cc in WIDTHS] + [(cc, 2, 11) for cc in WIDTHS])
+FUSED_UNTESTED = []  # [(row, reason)]: instantiations whose construction cannot meet its conditions (none)
+FUSED_NULL_XOUT = [(32, 2, 0), (16, 3, 0)]  # one row per MODE_DY >= 2 launched without xout
+FUSED_REJECTS = [(64, 2, 1), (16, 3, 1), (32, 0, 3), (48, 0, 0)]  # no such instantiation
+FUSED_SEED_MAX = 9.0  # grad_seed: 1 .. 9
+FUSED_SEED = 660067  # every row meets check_fused in both work forms (the per-member channel picks depend on it)
+# The sum(dz xhat) row is held to FACTOR_RSQRT x the deviation of a float32 evaluation.  One fp32 rounding of the summed
+# magnitude is 2^-24 of it, so an operand set whose float32 evaluation lands within 2^-26 of float64 would hold the
+# kernel (other summation order, rsqrtf) to less than ONE rounding: it would measure the yardstick's luck, not the
+# kernel.  check_fused refuses such sets; the (C, mode, epi, uniform) sets listed here take the first seed offset
+# (1, 2, ...) at which both replica counts (8, 64) meet every condition of check_fused.
+XHAT_YARD_MIN = 2.0 ** -26
+FUSED_SALT = {(16, 0, 0, True): 1, (16, 3, 0, False): 1, (16, 2, 0, False): 1, (16, 2, 0, True): 1, (16, 2, 1, True): 3}
+
+
+def fused_has_stats(epi):
+    """Identity-mask epilogues (EPI & 2) write statistics only with the chain bit."""
+    return not (epi & 2) or bool(epi & 8)
+
+
+def _ident_mask(c, seed):
+    """EPI & 2: the layer input is the (v1, post-ReLU-free) block input itself -- small integers with negatives and
+    zeros; the X tile is relu(x), the mask x > 0 (scale 1, shift 0).  No statistics, gamma or beta exist."""
+    e = Case()
+    e.x = hints((c.n_img, c.H, c.H, c.C), -3, 3, seed + 14)
+    e.snap, e.xin = e.x, torch.relu(e.x)
+    e.cnt = torch.full((CAP,), NAN, dtype=torch.float64)
+    for s, f, e_ in ranges(c.slots, c.sizes):
+        e.cnt[s] = e_ - f
+    e.gamma = e.beta = torch.full((CAP, c.C), NAN, dtype=torch.float64)
+    e.st_in = None
+    return e
+
+
+@functools.lru_cache(maxsize=None)
+def fused_case(cc, mode, epi, uniform=False, nrep=8):
+    """One operand set for both halves of a conv_bwd_fused launch: the dgrad half of ``dg_case`` (y, xout, the
+    statistics rows) and the wgrad half of ``wg_job`` (dW from the same dY and the same x), over one work list grouped
+    by member (slot 2 first) with its slab reduce table.  EPI & 2: identity mask; EPI & 8: ``c.chain`` holds the
+    chained BN (its input x3 = chain.x, its forward statistics), whose backward sums the launch adds."""
+    c = Case()
+    _geo(c, cc, 8, uniform, nrep)
+    c.mode, c.epi = mode, epi
+    seed = (cc * 139 + mode * 23 + epi * 7) * 1019 + uniform * 7919 + FUSED_SEED
+    seed += 104729 * FUSED_SALT.get((cc, mode, epi, bool(uniform)), 0)
+    c.ep = _ident_mask(c, seed) if epi & 2 else _mask_bn(c, seed)
+    c.chain = _mask_bn(c, seed + 577) if epi & 8 else None
+    if mode == 0:
+        _plain_dy(c, seed)
+    else:
+        _bn_bwd_input(c, seed, mode == 3)
+    if epi & 8:
+        c.x3 = c.chain.x
+    c.unit = 1.0 if mode == 0 else 0.5  # of y
+    c.wunit = 0.5 if mode == 0 else 0.25  # of dW
+    c.w = kx._weights(c, seed, 12 if mode == 0 else 10)  # IHWO: [CAP][Ci][3][3][Co]
+    c.res = hints((c.n_img, c.H, c.H, cc), -8, 8, seed + 3) if epi & 1 else None
+    _dgrad_ref(c)
+    _dw_ref(c)
+    c.w[c.idle] = NAN
+    c.st_seed = 1.0 + hints((CAP, nrep, 2, 64), 0, 4, seed + 4)
+    _work(c, grouped=True)
+    c.red = [[m * c.u[0], c.u[0], 0, m] for m in c.slots] if uniform else red_table(c.items)
+    return c
+
+
+def check_ident_mask(c):
+    e = c.ep
+    for dt in (torch.bfloat16, torch.float16):
+        assert torch.equal(e.x.to(dt).double(), e.x)
+    assert bool((e.x == e.x.round()).all()) and e.x.abs().max() <= 3
+    assert bool((e.x < 0).any()) and bool((e.x == 0).any()) and bool((e.x > 0).any())
+    assert torch.equal(e.xin, torch.relu(e.x)) and torch.equal(e.snap > 0, e.x > 0)
+    assert e.st_in is None and bool(torch.isnan(e.gamma).all()) and bool(torch.isnan(e.beta).all())
+    assert bool(torch.isnan(e.cnt[c.idle])) and not bool(torch.isnan(e.cnt[list(c.slots)]).any())
+
+
+def fused_xhat(c, dtype):
+    """(value, magnitude) [CAP][64] of the sum(dz xhat) row of a fused case, all replicas summed and their seed
+    included: ``dg_xhat``'s formula (xhat = x inv + (-mean inv) from the fp32 statistic words, the replicas added in
+    order; EPI bit 8: x and the statistics of ``c.chain``) with the pixels added ONE AT A TIME in raster order.  Every
+    step is a single correctly rounded elementwise operation, so the float32 figure is the same on every host (a
+    library reduction's order depends on the host's vector width and thread count).  Computed once per case."""
+    memo = c.__dict__.setdefault("_xhat", {})
+    if dtype in memo:
+        return memo[dtype]
+    cc = c.C
+    bn = c.chain or c.ep
+    val = c.st_seed[:, :, 1].sum(1).to(dtype)
+    mag = c.st_seed[:, :, 1].abs().sum(1).double()
+    eps = torch.tensor(BN_EPS, dtype=torch.float32).to(dtype)
+    for s, f, e in ranges(c.slots, c.sizes):
+        n = float((e - f) * c.H * c.H)
+        w = bn.st_in[s].to(dtype)
+        sm, q = torch.zeros(cc, dtype=dtype), torch.zeros(cc, dtype=dtype)
+        for r in range(c.nrep):
+            sm, q = sm + w[r, 0, :cc], q + w[r, 1, :cc]
+        mean = sm / n
+        inv = 1.0 / torch.sqrt((q / n - mean * mean).clamp(min=0.0) + eps)
+        y, x = c.y[f:e].to(dtype), bn.x[f:e].to(dtype)
+        t = (y * (x * inv + (-mean * inv))).reshape(e - f, -1, cc)
+        mag[s, :cc] += ((y * x * inv).abs() + (y * mean * inv).abs()).double().sum((0, 1, 2))
+        for i in range(e - f):
+            acc = torch.zeros(cc, dtype=dtype)
+            for p in range(t.shape[1]):
+                acc += t[i, p]
+            val[s, :cc] += acc
+    memo[dtype] = (val, mag)
+    return memo[dtype]
+
+
+def fused_xhat_yardstick(c):
+    """The scaled deviation of the float32 evaluation of the sum(dz xhat) row from the float64 one."""
+    (r64, mag), (r32, _) = fused_xhat(c, torch.float64), fused_xhat(c, torch.float32)
+    zero = mag == 0
+    assert torch.equal(r32.double()[zero], r64[zero])
+    return float(((r32.double() - r64).abs()[~zero] / mag[~zero]).max())
+
+
+def check_fused(c, seed_max=FUSED_SEED_MAX):
+    """Everything ``check_dg`` and ``check_wg`` assert, on the shared operands and the references alone."""
+    u, wu = c.unit, c.wunit
+    check_dy(c)
+    if c.epi & 2:
+        check_ident_mask(c)
+    else:
+        check_mask_bn(c)
+    if c.epi & 8:
+        assert c.mode == 2 and c.x3 is c.chain.x
+        check_mask_bn(c, c.chain)  # representable x3, uneven shares, one negative-variance channel per member
+        assert not torch.equal(c.chain.x, c.ep.x)
+    act = list(c.slots)
+    for t in (c.w[act], c.y, c.dy, c.ep.xin) + ((c.res,) if c.epi & 1 else ()):
+        for dt in (torch.bfloat16, torch.float16):
+            assert torch.equal(t.to(dt).double(), t), "operand not representable"
+    # ---- dgrad half
+    assert bool((c.w[act] == c.w[act].round()).all()) and bool((c.y / u == (c.y / u).round()).all())
+    assert c.absy.max() < EXACT * u and c.absy.max() <= 256 * u, float(c.absy.max())
+    seed_abs = c.st_seed.abs().sum(1).max()
+    assert c.st_abs.max() + seed_abs < EXACT * u
+    assert bool((c.st_seed != 0).all()) and bool((c.st_seed == c.st_seed.round()).all())
+    for sl in c.slots:
+        assert bool(((c.w[sl] != 0).sum((0, 1, 2)) > 0).all()) and bool(((c.w[sl] != 0).sum((1, 2, 3)) > 0).all())
+        assert bool(((c.w[sl] != 0).sum((0, 3)) > 0).all()), "a tap without a weight"
+    assert not torch.equal(c.w[c.slots[0]], c.w[c.slots[1]]) and bool(torch.isnan(c.w[c.idle]).all())
+    assert bool((c.y != 0).any()) and bool(((c.ep.snap <= 0) & (c.absy > 0)).any()), "the mask removes something"
+    if fused_has_stats(c.epi):
+        yard = fused_xhat_yardstick(c)
+        assert yard >= XHAT_YARD_MIN, "the float32 yardstick of sum(dz xhat) is atypically close to float64: %.3e" % yard
+    # ---- wgrad half
+    assert bool((c.dw / wu == (c.dw / wu).round()).all())
+    assert c.absdw.max() + seed_max < EXACT * wu, float(c.absdw.max())
+    for sl in c.slots:
+        assert bool((c.dw[sl] != 0).any((0, 3)).all()), "a tap without a gradient"
+    assert not torch.equal(c.dw[c.slots[0]], c.dw[c.slots[1]])
+    # ---- the work list and its slab reduce table
+    check_work(c, grouped=True)
+    assert [r[3] for r in c.red] == ([0, 1] if c.uniform else [2, 0]) and sum(r[1] for r in c.red) == len(c.items)
+    for first, n, _, slot in c.red:
+        assert all(it[3] == slot for it in c.items[first:first + n])
+
+
+def lds_fused(cc, wpitch, wlds):
+    """hip_resnet._conv_bwd_fused: four tiles, the raw-x interiors at C >= 64, the dgrad weights at C = 16 (WLDS)."""
+    cpad = {16: 16, 32: 48, 64: 80}[cc]
+    n = 2304 + (4 * tile_elems(cc, 8, wpitch) + (2 * 8 * (512 // cc) * cpad if cc >= 64 else 0)) * 2
+    if cc == 16 and wlds:
+        n += 16 * (32 * 5 + 8) * 2
+    assert n <= 160 * 1024, n
+    return n
+
+
+# trailing reduction of a fused launch: (launch C, r_c, [(slot, n slabs)], r_nblk).  r_c == C and != C in both
+# directions, one r_c = 64 table; slab counts on both sides of slab_reduce_wg's loop bounds (g + 8 < n, stride 16 over
+# 8 thread groups), one row without slabs; r_nblk = E / 32 (the plan's) and values that do not divide it (looping)
+FUSED_TRAIL = [(16, 16, [(0, 1), (2, 17)], 96), (32, 16, [(2, 8), (0, 25)], 7), (16, 32, [(0, 9), (2, 16)], 320),
+               (32, 32, [(2, 24), (0, 0)], 48), (64, 64, [(0, 9), (2, 1)], 100)]
+FUSED_TRAIL_FULL = (16, 32, [(2, 24), (0, 9)], 37)  # full-mantissa slabs
+
+
+@functools.lru_cache(maxsize=None)
+def trail_case(cc, rc, members, nblk, full_mantissa=False):
+    """The slabs of ANOTHER conv (width rc) reduced by the trailing workgroups of a width-cc launch: the gradient row
+    holds the launch's own block at g_off and the other conv's at r_goff."""
+    k = Case()
+    k.full, k.C, k.rc, k.nblk = full_mantissa, cc, rc, nblk
+    (k.g_off, k.r_goff), k.row = grad_layout([cc, rc])
+    n = sum(m[1] for m in members)
+    if full_mantissa:
+        valid, _ = slab_index(rc)
+        slab = mant_slabs((n, slab_elems(rc)), 3700 + cc)
+        slab[:, ~valid] = NAN
+    else:
+        slab = int_slabs(rc, n, 3600 + cc + rc + nblk)
+    k.red = red_rows(members)
+    k.jobs = [("conv", rc, slab, k.red, k.r_goff)]
+    k.seed = grad_seed(k.row, 3800 + cc + 3 * rc + nblk)
+    k.want, k.mag = k.seed.clone(), k.seed.abs()
+    k.nslab = torch.zeros_like(k.seed)
+    conv_reduce_ref(k.want, k.mag, rc, slab, k.red, k.r_goff)
+    for _, m, _, slot in k.red:
+        k.nslab[slot, k.r_goff:k.r_goff + 9 * rc * rc] = m
+    assert k.g_off != k.r_goff and nblk > 0
+    return k

@@ -15,6 +15,9 @@ between the convs (``convg_aux.hip``), which also update the running statistics 
 The dense layer is the grouped bf16 GEMM (gemm.hip) with softmax-CE in between.  The whole step is captured
 into one HIP graph per batch composition.  Eval (``evaluate_population``) runs the same forward kernels for every
 member at once with BN coefficients from the moving statistics.
+
+ResNet-18 / 34 (v2 building blocks, reference ``_building_block_v2``: two 3x3 convs per block) run the same stem, head
+and kernels under ``_bb_forward`` / ``_bb_backward``; their 7 x 7 stride-1 convs take convg_t3's packs of whole images.
 """
 
 from __future__ import annotations
@@ -59,7 +62,9 @@ _CG_STEM_BAND = os.environ.get("DTF_CG_STEM_BAND", "1") == "1"
 _CG_STEM_WG = int(os.environ.get("DTF_CG_STEM_WG", "2048"))
 _CG_WPK_WO64 = 32  # pixels per k-step of the 64-row tiles
 # stride-1 3x3 forward / data gradient with LDS-resident input rows (convg_t3_kernel): image width -> rows per tile
-_CG_T3 = {56: 8, 28: 7, 14: 14}  # must match dtf_convg_t3 (rows divide the image height)
+# (at width 7 an item is a pack of dtf_convg_t3_pack() whole images of one member; the building-block plans only: the
+# bottleneck plans keep the generic kernel for their 7 x 7 convs.  Without the entry those convs run the generic kernel)
+_CG_T3 = {56: 8, 28: 7, 14: 14, 7: 7}  # must match dtf_convg_t3 (rows divide the image height)
 # convg_t3 forward: bit 0 = LDS-staged weights (the pre-round-4 form) instead of direct fragment loads (A/B switch)
 # Folded forward (v2 training): every BN+ReLU is applied while the consuming convolution -- and, in the backward, its
 # weight gradient -- stages its input (convg MODE 1, convg_t3 XF, convg_wgrad_wide MX 1), so no relu(BN(.)) tensor
@@ -234,6 +239,7 @@ def _register():
     reg("dtf_cg_bn_bwd_sums", [P(BnSumArgs), c_int, c_void_p])
     reg("dtf_cg_det_finish", [c_void_p, c_void_p, c_long, c_long, c_void_p, c_int, c_void_p, c_void_p, c_void_p])
     reg("dtf_fixed_acc", [])
+    reg("dtf_convg_t3_pack", [])
     for n in ("dtf_cg_args_size", "dtf_bnfin_args_size", "dtf_ew_args_size", "dtf_gap_args_size",
               "dtf_bnadd_args_size", "dtf_bnsum_args_size"):
         reg(n, [])
@@ -261,9 +267,10 @@ class HipImageNetBackend(HipBackend):
         super().__init__(engine)
         prog = engine.arch.prog
         cfg = prog.cfg
-        if not (cfg.bottleneck and cfg.version in (1, 2) and cfg.first_pool_size == 3 and cfg.first_pool_stride == 2
-                and cfg.kernel_size == 7 and cfg.conv_stride == 2):
-            raise ValueError("HIP ImageNet backend supports the v1 / v2 bottleneck ImageNet configurations")
+        if not (cfg.version in ((1, 2) if cfg.bottleneck else (2,)) and cfg.first_pool_size == 3
+                and cfg.first_pool_stride == 2 and cfg.kernel_size == 7 and cfg.conv_stride == 2):
+            raise ValueError("HIP ImageNet backend supports the v1 / v2 bottleneck and the v2 building-block ImageNet "
+                             "configurations (7x7/2 stem, 3x3/2 max-pool); v1 building blocks run on the torch backend")
         if cfg.image_size % 32:
             raise ValueError("image size must be a multiple of 32")
         self.prog, self.cfg = prog, cfg
@@ -410,10 +417,13 @@ class _ImageNetPlan(HipPlan):
         # every output-channel tile and its coefficient LDS costs occupancy; profiles/r2_imagenet_fold_ab.log)
         self.ax, self.a1, self.a2 = [], [], []
         # folded forward (CG_FOLD): v2 training plans keep no relu(BN(.)) tensors
-        self.fold = CG_FOLD and not self.eval and not be.v1
-        self.fold2 = CG_FOLD2 and not self.fold and not self.eval and not be.v1
-        self.fold1 = CG_FOLD1 and not self.fold and not self.eval and not be.v1 and self.FOLD1_OK
-        self.fold3 = CG_FOLD3_MAXC > 0 and not self.fold and not self.eval and not be.v1 and self.FOLD1_OK
+        # building blocks (ResNet-18 / 34, v2): two 3x3 convs per block; BN + ReLU stay materialised
+        self.bb = not cfg.bottleneck
+        self.fold = CG_FOLD and not self.eval and not be.v1 and not self.bb
+        self.fold2 = CG_FOLD2 and not self.fold and not self.eval and not be.v1 and not self.bb
+        self.fold1 = CG_FOLD1 and not self.fold and not self.eval and not be.v1 and self.FOLD1_OK and not self.bb
+        self.fold3 = (CG_FOLD3_MAXC > 0 and not self.fold and not self.eval and not be.v1 and self.FOLD1_OK
+                      and not self.bb)
         # v1 (post-activation): h3 = conv3 output (BN3 input), sc = raw projection output (BN_p input), a0 = the
         # stem's relu(BN(y0)); no ax (the block input IS a ReLU output)
         self.v1 = be.v1
@@ -422,8 +432,18 @@ class _ImageNetPlan(HipPlan):
         hw, cin = H2, cfg.num_filters
         self.geo = []  # per block: (H_in, H_out, cin, f, fout)
         for bi, blk in enumerate(prog.blocks):
-            c1, c2, c3 = (prog.convs[i] for i in blk.convs)
             ho = hw // blk.stride
+            if self.bb:  # h1 = conv1 output (at the block's output resolution), a1 = relu(BN2(h1)); no h2 / a2
+                c1, c2 = (prog.convs[i] for i in blk.convs)
+                self.h1.append(act("h1", ho, c1.cout))
+                self.a1.append(act("a1", ho, c1.cout))
+                self.ax.append(act("ax", hw, cin))
+                self.sc.append(act("sc", ho, c2.cout) if blk.proj is not None else None)
+                self.xs.append(act("x", ho, c2.cout, bi + 1))
+                self.geo.append((hw, ho, cin, c1.cout, c2.cout))
+                hw, cin = ho, c2.cout
+                continue
+            c1, c2, c3 = (prog.convs[i] for i in blk.convs)
             self.h1.append(act("h1", hw, c1.cout))
             self.h2.append(act("h2", ho, c2.cout))
             self.ax.append(act("ax", hw, cin) if not (self.v1 or self.fold) else None)
@@ -485,15 +505,18 @@ class _ImageNetPlan(HipPlan):
         items = self._xcd_order(items, -(-co // tc))
         return self._hold(torch.tensor(items, dtype=torch.int32, device=self.be.dev))
 
-    def _band_work(self, hw, rows, co, tc):
-        """(slot, p0, p1, o0) tiles of `rows` whole image rows x tc output channels (convg_t3_kernel)."""
+    def _band_work(self, hw, rows, co, tc, pack=1):
+        """(slot, p0, p1, o0) tiles of `rows` whole image rows x tc output channels (convg_t3_kernel); ``pack`` > 1
+        (rows == hw): up to that many whole consecutive images of one member per item, the last pack of a member
+        ragged."""
         items = []
         for s, n in zip(self.slots, self.sizes):
-            for img in range(self.first[s], self.first[s] + n):
+            for img in range(self.first[s], self.first[s] + n, pack):
+                last = min(img + pack, self.first[s] + n) - 1
                 for y0 in range(0, hw, rows):
                     p0 = (img * hw + y0) * hw
                     for o0 in range(0, co, tc):
-                        items.append([s, p0, p0 + min(rows, hw - y0) * hw, o0])
+                        items.append([s, p0, (last * hw + y0 + min(rows, hw - y0)) * hw, o0])
         items = self._xcd_order(items, -(-co // tc))
         return self._hold(torch.tensor(items, dtype=torch.int32, device=self.be.dev))
 
@@ -610,10 +633,11 @@ class _ImageNetPlan(HipPlan):
         a.log2ci = _log2(a.Ci)
         tc = 128 if a.Co >= 128 and max(hw_in, hw_out) > _CG_TC64_HW else 64
         if (k == 3 and c.stride == 1 and (mode == 0 or (mode == 1 and not dgrad)) and hw_in in _CG_T3
-                and ci != be.prog.stem and epi == (6 if dgrad else 4) and a.Ci % 32 == 0 and a.Ci <= 512):
+                and ci != be.prog.stem and epi in ((6,) if dgrad else (4, 5)) and a.Ci % 32 == 0 and a.Ci <= 512
+                and (hw_in != 7 or self.bb) and (mode == 0 or (epi == 4 and hw_in != 7))):
             rows = _CG_T3[hw_in]
             tc = 64 if hw_in == 56 else 128  # must match dtf_convg_t3's instantiations
-            work = self._band_work(hw_in, rows, a.Co, tc)
+            work = self._band_work(hw_in, rows, a.Co, tc, pack=ops.lib().dtf_convg_t3_pack() if hw_in == 7 else 1)
             a.work = _p(work)
             self._hold(a)
             self._add(ops.lib().dtf_convg_t3, ctypes.byref(a), tc, epi, int(dgrad), hw_in, work.shape[0], mode)
@@ -924,13 +948,16 @@ class _ImageNetPlan(HipPlan):
         nblk = len(prog.blocks)
         for i, blk in enumerate(prog.blocks):
             hi, ho, cin, f, fout = self.geo[i]
-            b1, b2, b3 = blk.bns
-            c1, c2, c3 = blk.convs
             x = self.xs[i]
             relu = L.dtf_cg_bn_relu_apply
             nxt = prog.blocks[i + 1].bns[0] if i + 1 < nblk else prog.final_bn
             res = self.sc[i] if blk.proj is not None else x
-            self.bn_final(b1, hi, False)
+            self.bn_final(blk.bns[0], hi, False)
+            if self.bb:
+                self._bb_forward(i, self.sf(blk.bns[1]), self.sf(nxt))
+                continue
+            b1, b2, b3 = blk.bns
+            c1, c2, c3 = blk.convs
             if self.fold:
                 if blk.proj is not None:
                     self.conv(blk.proj, x, self.sc[i], hi, mode=1, c_in=self.cf(b1), epi=0)
@@ -986,6 +1013,9 @@ class _ImageNetPlan(HipPlan):
         gpend = None  # a block-input gradient left to its consumer (CG_GFOLD_MAXF): (dz1, x, BN1 coefficients, add)
         for i in range(nblk - 1, -1, -1):
             blk = prog.blocks[i]
+            if self.bb:
+                gcur = self._bb_backward(i, gcur)
+                continue
             hi, ho, cin, f, fout = self.geo[i]
             b1, b2, b3 = blk.bns
             c1, c2, c3 = blk.convs
@@ -1073,6 +1103,9 @@ class _ImageNetPlan(HipPlan):
         self.maxpool(self.y0, self.xs[0], H1, H2)
         relu = L.dtf_cg_bn_relu_apply
         for i, blk in enumerate(prog.blocks):
+            if self.bb:
+                self._bb_forward(i, sink, sink)
+                continue
             hi, ho, cin, f, fout = self.geo[i]
             b1, b2, b3 = blk.bns
             c1, c2, c3 = blk.convs
@@ -1095,6 +1128,64 @@ class _ImageNetPlan(HipPlan):
         self._hold(g)
         self.gap(g, 0)
         self.dense_head(False)
+
+    # ------------------------------------------------------------------------- v2 building blocks (ResNet-18 / 34)
+    def _bb_forward(self, i, st2, st_next):
+        """Block i of the v2 building-block net (reference ``_building_block_v2``): a = relu(BN1(x)); shortcut = x, or
+        the 1x1 / s projection of a in a stage's first block; h1 = conv3x3 / s (a); a1 = relu(BN2(h1));
+        y = conv3x3 (a1) + shortcut.  BN1's coefficients are final (training: bn_final by the caller; eval: the moving
+        statistics).  st2 / st_next: where conv1 / conv2 reduce the statistics of BN2 / the next block's BN1 (eval: a
+        sink).  conv2 adds the shortcut in its epilogue (EPI 5) -- on the row-resident kernel where _CG_T3 has the
+        width (7: packs of whole images), else on the generic one."""
+        prog = self.be.prog
+        blk = prog.blocks[i]
+        hi, ho, cin, f, _ = self.geo[i]
+        b1, b2 = blk.bns
+        c1, c2 = blk.convs
+        x = self.xs[i]
+        relu = ops.lib().dtf_cg_bn_relu_apply
+        self.ew(relu, x, self.ax[i], self.cf(b1), hi, cin)
+        if blk.proj is not None:
+            self.conv(blk.proj, self.ax[i], self.sc[i], hi, mode=0, epi=0)
+        self.conv(c1, self.ax[i], self.h1[i], hi, mode=0, epi=4, st=st2)
+        if not self.eval:
+            self.bn_final(b2, ho, False)
+        self.ew(relu, self.h1[i], self.a1[i], self.cf(b2), ho, f)
+        self.conv(c2, self.a1[i], self.xs[i + 1], ho, mode=0, epi=5,
+                  res=self.sc[i] if blk.proj is not None else x, st=st_next)
+
+    def _bb_backward(self, i, g):
+        """Backward of building block i from g = dL/dy; returns dL/dx.  conv2: dz2 = dgrad(g) masked by BN2(h1) > 0
+        with the BN2-backward sums (EPI 6), dh1 = BN2-backward(dz2, h1).  conv1: dz1 = dgrad(dh1) [+ the projection's
+        data gradient] masked by BN1(x) > 0 with the BN1 sums (a strided conv1: the transposed gather), then
+        dx = BN1-backward(dz1, x) [+ g through an identity shortcut]."""
+        prog = self.be.prog
+        blk = prog.blocks[i]
+        hi, ho, cin, f, _ = self.geo[i]
+        b1, b2 = blk.bns
+        c1, c2 = blk.convs
+        x, h1 = self.xs[i], self.h1[i]
+        bwd = ops.lib().dtf_cg_bn_bwd_apply
+        dz2 = self.tmp("dz2", ho, f)
+        self.conv(c2, g, dz2, ho, mode=0, epi=6, xm=h1, c_ep=self.cf(b2), st=self.sb(b2), dgrad=True)
+        self.bn_final(b2, ho, True)
+        dh1 = self.tmp("dh1", ho, f)
+        self.ew(bwd, h1, dh1, self.cb(b2), ho, f, dz=dz2)
+        self.wgrad(c2, self.a1[i], g, ho)
+        pd = None
+        if blk.proj is not None:
+            # (conv1 of a stride-2 block gathers transposed, which reads no compact residual: full resolution)
+            pd = self.tmp("pd", hi, cin)
+            self.conv(blk.proj, g, pd, ho, mode=0, epi=0, dgrad=True)
+            self.wgrad(blk.proj, self.ax[i], g, hi)
+        dz1 = self.tmp("dz1", hi, cin)
+        self.conv(c1, dh1, dz1, ho, mode=0, epi=6 | (1 if pd is not None else 0), res=pd, xm=x, c_ep=self.cf(b1),
+                  st=self.sb(b1), dgrad=True)
+        self.bn_final(b1, hi, True)
+        self.wgrad(c1, self.ax[i], dh1, hi)
+        gnext = self.tmp("gA" if (i % 2 == 0) else "gB", hi, cin)
+        self.ew(bwd, x, gnext, self.cb(b1), hi, cin, dz=dz1, add=None if blk.proj is not None else g)
+        return gnext
 
     # ------------------------------------------------------------------------------------ ResNet v1 program
     def bn_add_relu(self, h, s, out, coef_h, coef_s, hw, C):

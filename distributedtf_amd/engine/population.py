@@ -389,7 +389,9 @@ def make_backend(engine: PopulationEngine, name: str):
         if getattr(engine.arch, "name", "") == "mnist_cnn":
             from .hip_mnist import HipMnistBackend
             return HipMnistBackend(engine)
-        if getattr(getattr(engine.arch, "cfg", None), "bottleneck", False):
+        cfg = getattr(engine.arch, "cfg", None)
+        # the ImageNet-shape nets: bottleneck, or building blocks behind the 7x7/2 stem and max-pool (ResNet-18 / 34)
+        if getattr(cfg, "bottleneck", False) or getattr(cfg, "first_pool_size", None):
             from .hip_imagenet import HipImageNetBackend
             return HipImageNetBackend(engine)
         from .hip_resnet import HipResNetBackend

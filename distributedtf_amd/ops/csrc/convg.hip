@@ -841,6 +841,7 @@ __host__ __device__ constexpr int t3_nhalf() {
   return -1;
 }
 
+#define DTF_T3_PACK 4  // 7 x 7 images per work item of the packed instance (dtf_convg_t3_pack(): the plan reads it)
 #ifndef T3_DIRECT_A
 #define T3_DIRECT_A 1  // forward t3: A fragments loaded directly from the weight rows (no LDS staging of A)
 #endif
@@ -883,11 +884,30 @@ __device__ unsigned long long dtf_t3_stamps[T3_STAMP_WGS][8];
 #endif
 
 // XF: the staged input rows get BN + ReLU (coefficients c_in: scale / shift of the input's BN) -- the folded forward
-template <int TC, int EPI, bool AKM, int W, int R, int TP, int WRN, bool XF = false>
-__global__ __launch_bounds__(256, 2) void convg_t3_kernel(CgArgs a) {
+//
+// G > 1 (7 x 7 images, R = W = 7): a work item is a PACK of up to G whole consecutive images of one member -- one
+// image is 49 pixels, three MFMA column tiles of which the third is mostly padding, and too little work for a
+// workgroup.  G = 4 puts 196 real pixels into the 224-pixel tile of the 28 / 14-wide instances (87.5 % of the MFMA
+// columns real, the same 28 accumulator tiles per wave, 2 workgroups per CU).  Every image's 9 x 9 halo is staged
+// at row pitch WT = 15 pixels and IMAGE pitch IP = 8 WT + 1 = 121 pixels (the bottom halo row of an image overlaps
+// the top halo row of the next one: both zero).  A 16-pixel fragment wraps across image rows and across images, so
+// a lane's staged base comes from p -> (image, y, x); the taps still add one constant.  The ds_read_b128 lane
+// groups read pixels {s..s+3, s+12..s+15} with k-chunk j against {s+4..s+11} with chunk j + 1; at the 96-byte pixel
+// pitch a pixel's bank quad is 6 pos + j (mod 16), so a group is conflict-free iff its staged positions are distinct
+// mod 8: every step from a pixel to the next must be 1 (mod 8) -- W + 8 across a row end, and IP = 1 (mod 8)
+// across an image end (pos(g+1, 0, 0) - pos(g, 6, 6) = IP - 96).  The tile's padding pixels continue the last
+// image's positions, 32 staged pixels back (same residues, inside the tile).  Part of what they read there --
+// columns 9 .. 14 of the staged rows -- is written by no thread: UNINITIALISED LDS, possibly NaN.  That is
+// harmless because an MFMA column only feeds its own output pixel and the epilogue drops pixels p >= p1 (at G = 1
+// the padding pixels read pixel 0 instead).
+// tools/t3_bank_check.py checks every fragment start and tap.  A ragged last pack stages zeros for its missing
+// images; the epilogue's p < p1 keeps them out of the output and the statistics.
+template <int TC, int EPI, bool AKM, int W, int R, int TP, int WRN, bool XF, int G>
+__device__ __forceinline__ void convg_t3_body(const CgArgs& a) {
   constexpr int BK = 32;
   constexpr int PW = TP / (4 / WRN), NTP = PW / 16, MT = TC / WRN / 16;
-  static_assert(PW % 16 == 0 && TP >= R * W && W % R == 0, "pixel tile: whole rows, bands divide the image");
+  static_assert(PW % 16 == 0 && TP >= G * R * W && W % R == 0, "pixel tile: whole rows, bands divide the image");
+  static_assert(G == 1 || (R == W && TP - G * R * W <= 32), "packs: whole images, at most 32 padding pixels");
   constexpr int RP = BK + 16;  // A row / staged-pixel pitch (bf16; 96 B = 6 bank quads per pixel)
   constexpr int CPR = BK / 8, RPT = 256 / CPR;
   constexpr int KPA = TC + 8;
@@ -897,9 +917,12 @@ __global__ __launch_bounds__(256, 2) void convg_t3_kernel(CgArgs a) {
   // against pixels i' with chunk j + 1) hits 16 distinct bank quads for every tap offset and for fragments that
   // wrap to the next image row (the former 80 B / W + 16 pitches were 2-way: 1,193-4,432 conflicts per wave,
   // profiles/r3_pmc_imagenet_t3.txt; exhaustive check over tap offsets / fragment starts in tools/t3_bank_check.py)
-  constexpr int WS = W + 2, WT = W + 8, RT = R + 2, NBP = RT * WS;
+  constexpr int WS = W + 2, WT = W + 8, RT = R + 2, NBP = G * RT * WS;
   constexpr int NBC = NBP * CPR, MAXB = (NBC + 255) / 256;
-  constexpr int SBT = RT * WT * RP + 8;  // + slack for the inactive staging slots
+  constexpr int IP = G > 1 ? (RT - 1) * WT + 1 : 0;   // pack: staged pixels from an image to the next
+  constexpr int NPOS = (G - 1) * IP + RT * WT;        // staged pixels of the tile
+  static_assert(G == 1 || (IP % 8 == 1 && WT % 8 == W % 8), "pack pitches: conflict-free fragment reads");
+  constexpr int SBT = NPOS * RP + 8;  // + slack for the inactive staging slots
   constexpr int SOPS = 2 * SA + SBT;
   constexpr int NHALF = t3_nhalf<TP, TC, (T3_EPI_LDS > SOPS ? T3_EPI_LDS : SOPS)>();
   static_assert(NHALF > 0, "epilogue staging split");
@@ -911,7 +934,9 @@ __global__ __launch_bounds__(256, 2) void convg_t3_kernel(CgArgs a) {
   T3_STAMP_DECL
   T3_STAMP(0);
   const int4 wk = a.work[blockIdx.x];
-  DTF_WG_CHECK(wk.x >= 0 && wk.y >= 0 && wk.z > wk.y && wk.z - wk.y <= R * W && a.Wi == W && a.Hi % R == 0);
+  DTF_WG_CHECK(wk.x >= 0 && wk.y >= 0 && wk.z > wk.y && wk.z - wk.y <= G * R * W && a.Wi == W && a.Hi % R == 0);
+  // a pack: whole images (p0 on an image boundary, a multiple of R * W pixels) of a R x W image
+  DTF_WG_CHECK(G == 1 || (a.Hi == R && wk.y % (R * W) == 0 && (wk.z - wk.y) % (R * W) == 0));
   const int slot = wk.x, p0 = wk.y, p1 = wk.z, o0 = wk.w;
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int wr = wave % WRN, wc = wave / WRN;
@@ -925,11 +950,14 @@ __global__ __launch_bounds__(256, 2) void convg_t3_kernel(CgArgs a) {
 #pragma unroll
   for (int j = 0; j < MAXB; ++j) {
     const int idx = tid + 256 * j;
-    const int pix = idx / CPR, c8 = idx % CPR, r = pix / WS, col = pix % WS;
+    const int pix = idx / CPR, c8 = idx % CPR;
+    const int gi = G > 1 ? pix / (RT * WS) : 0;  // image of the pack
+    const int pin = pix - gi * (RT * WS), r = pin / WS, col = pin % WS;
     const int gy = y0 - 1 + r, gx = col - 1;
-    const bool ok = idx < NBC && gy >= 0 && gy < H && gx >= 0 && gx < W;
-    bl[j] = idx < NBC ? (r * WT + col) * RP + 8 * c8 : RT * WT * RP;
-    bg[j] = ok ? (gy * W + gx) * Ci + 8 * c8 : 0;
+    // (a pack's missing images -- a ragged last pack -- stage zeros)
+    const bool ok = idx < NBC && gy >= 0 && gy < H && gx >= 0 && gx < W && (G == 1 || p0 + gi * (R * W) < p1);
+    bl[j] = idx < NBC ? (gi * IP + r * WT + col) * RP + 8 * c8 : NPOS * RP;
+    bg[j] = ok ? ((gi * R + gy) * W + gx) * Ci + 8 * c8 : 0;
     bok |= (unsigned)ok << j;
   }
   // XF: the input BN's scale / shift of every channel in LDS (Ci <= 512), read at staging time (held in registers
@@ -999,8 +1027,16 @@ __global__ __launch_bounds__(256, 2) void convg_t3_kernel(CgArgs a) {
 #pragma unroll
   for (int n = 0; n < NTP; ++n) {
     int p = wc * PW + 16 * n + (lane & 15);
-    p = p < R * W ? p : 0;  // padding pixels (discarded by the epilogue) read pixel 0
-    bpo[n] = ((p / W) * WT + p % W) * RP + 8 * (lane >> 4);
+    if constexpr (G > 1) {
+      const int gi = p / (R * W), pin = p - gi * (R * W);
+      int pos = gi * IP + (pin / W) * WT + pin % W;
+      // padding pixels: the positions after the last real pixel's, 32 back
+      if (p >= G * R * W) pos = (G - 1) * IP + (R - 1) * WT + W - 1 + (p - (G * R * W - 1)) - 32;
+      bpo[n] = pos * RP + 8 * (lane >> 4);
+    } else {
+      p = p < R * W ? p : 0;  // padding pixels (discarded by the epilogue) read pixel 0
+      bpo[n] = ((p / W) * WT + p % W) * RP + 8 * (lane >> 4);
+    }
   }
   f32x4_t acc[MT][NTP];
 #pragma unroll
@@ -1130,6 +1166,24 @@ __global__ __launch_bounds__(256, 2) void convg_t3_kernel(CgArgs a) {
                                                    p1, 0, 0, 0, 0);
   T3_STAMP(3);
   T3_STAMP_FLUSH();
+}
+
+template <int TC, int EPI, bool AKM, int W, int R, int TP, int WRN, bool XF = false>
+__global__ __launch_bounds__(256, 2) void convg_t3_kernel(CgArgs a) {
+  convg_t3_body<TC, EPI, AKM, W, R, TP, WRN, XF, 1>(a);
+}
+
+// The instantiations added after the ones above were tuned (EPI 5; the packs, G > 1) are generated without the
+// compiler's packed fp32 VALU forms (v_pk_add / mul / fma_f32); the exact tests run them as built.  The attribute
+// means nothing to the host pass.
+#ifdef __HIP_DEVICE_COMPILE__
+#define DTF_NO_PK_F32 __attribute__((target("no-packed-fp32-ops")))
+#else
+#define DTF_NO_PK_F32
+#endif
+template <int TC, int EPI, bool AKM, int W, int R, int TP, int WRN, int G>
+__global__ __launch_bounds__(256, 2) DTF_NO_PK_F32 void convg_t3n_kernel(CgArgs a) {
+  convg_t3_body<TC, EPI, AKM, W, R, TP, WRN, false, G>(a);
 }
 
 // ---------------------------------------------------------------------------------------------- wgrad
@@ -2003,8 +2057,13 @@ DTF_API int dtf_t3_stamp_read(void* dst, long bytes) {
 
 // Stride-1 3x3 conv / data gradient with LDS-resident input rows (convg_t3_kernel).  w: image width (56: 8-row
 // tiles of 448 pixels, 64-channel tiles; 28: 7 rows, 14: whole 14-row images, 224-pixel tiles of 128 channels);
-// epi 4 (forward, statistics) or 6 (data gradient: mask + statistics, akm = 1).
+// 7: packs of DTF_T3_PACK whole 7 x 7 images of one member, 224-pixel tiles of 128 channels -- work rows (slot, p0,
+// p1, o0) with p0 on an image boundary and p1 - p0 a multiple of 49, at most 49 DTF_T3_PACK);
+// epi 4 (forward, statistics), 5 (forward + residual, statistics of the sum) or 6 (data gradient: mask +
+// statistics, akm = 1).
 // mode 1 (forward only): BN + ReLU of the input applied while its rows are staged (c_in), the folded forward
+DTF_API int dtf_convg_t3_pack() { return DTF_T3_PACK; }  // the plan sizes its packs by this (hip_imagenet.py)
+
 DTF_API int dtf_convg_t3(const CgArgs* a, int tc, int epi, int akm, int w, int nwork, int mode, hipStream_t stream) {
   if (nwork <= 0) return 0;
   if (a->kh != 3 || a->kw != 3 || a->stride != 1 || a->pad != 1 || a->Wi != w || a->Hi != w || a->Ho != w ||
@@ -2026,6 +2085,20 @@ DTF_API int dtf_convg_t3(const CgArgs* a, int tc, int epi, int akm, int w, int n
   T3_GEO(6, true)
 #undef T3_GEO
 #undef T3_CASE
+  // the later instantiations (plain operand only: no plan folds BN into them): the residual epilogue at the band
+  // widths, and packs of whole 7 x 7 images with every epilogue
+#define T3N_CASE(TC_, E_, AK_, W_, R_, TP_, WRN_, G_)                                                        \
+  if (tc == TC_ && epi == E_ && akm == AK_ && w == W_ && mode == 0) {                                       \
+    hipLaunchKernelGGL((convg_t3n_kernel<TC_, E_, AK_, W_, R_, TP_, WRN_, G_>), grid, block, 0, stream, *a); \
+    return DTF_CHECK_LAUNCH();                                                                              \
+  }
+  T3N_CASE(64, 5, false, 56, 8, 448, 1, 1)
+  T3N_CASE(128, 5, false, 28, 7, 224, 2, 1)
+  T3N_CASE(128, 5, false, 14, 14, 224, 2, 1)
+  T3N_CASE(128, 4, false, 7, 7, 224, 2, DTF_T3_PACK)
+  T3N_CASE(128, 5, false, 7, 7, 224, 2, DTF_T3_PACK)
+  T3N_CASE(128, 6, true, 7, 7, 224, 2, DTF_T3_PACK)
+#undef T3N_CASE
   return -1;
 }
 

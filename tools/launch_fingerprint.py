@@ -258,6 +258,11 @@ def sections(dev):
         if not half:
             be = hip_imagenet_f32.HipImageNetF32Backend(engine(arch, 2, dev, torch.float32))
             yield from plans("imagenet50 v%d fp32" % version, be, [([0, 1], [2, 1])], [([0, 1], 2)])
+    # ---- ImageNet-shape ResNet-18 (v2 building blocks); 224: the row-band widths and the packed 7 x 7 kernel
+    for image in (64, 224):
+        arch = ResNetArch(imagenet_config(18, 2, num_classes=1001, image_size=image))
+        be = hip_imagenet.HipImageNetBackend(engine(arch, 2, dev, d16, **kw16))
+        yield from plans("imagenet18 v2 image %d" % image, be, [([0, 1], [5, 1])], [([0, 1], 2)])
 
 
 def main():

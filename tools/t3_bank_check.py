@@ -28,3 +28,27 @@ for W,R,TP in ((56,8,448),(28,7,224),(14,14,224)):
             res.append((worst, RP, WT))
     res.sort()
     print(W, res[:6], "current", [r for r in res if r[1]==40 and r[2]==W+16])
+# Packed 7 x 7 geometry (convg_t3_kernel G = 4: packs of whole images in a 224-pixel tile): staged position of pixel
+# p = 49 g + 7 y + x is g * IP + y * WT + x; padding pixels continue the last image's positions, 32 back.  At the
+# 96-byte pixel pitch the reads are conflict-free iff every pixel-to-pixel step is 1 (mod 8) staged pixels: WT = 15 and
+# IP = 121 (= 8 WT + 1) are the smallest such pitches that keep the 9 x 9 halos apart.
+W, NI, TP, RP = 7, 4, 224, 48
+res = []
+for WT in range(W + 2, W + 18):
+    for IP in range(8 * WT + 1, 8 * WT + 18):
+        worst = 1
+        for start in range(0, TP, 16):
+            for tap in range(9):
+                ty, tx = tap // 3, tap % 3
+                def addr(l, start=start):
+                    i = l % 16; j = l // 16
+                    p = start + i
+                    g, pin = p // 49, p % 49
+                    pos = g * IP + (pin // W) * WT + pin % W
+                    if p >= 49 * NI:
+                        pos = (NI - 1) * IP + 6 * WT + 6 + (p - (49 * NI - 1)) - 32
+                    return ((pos + ty * WT + tx) * RP + 8 * j) * 2
+                worst = max(worst, conf(addr))
+        res.append((worst, ((NI - 1) * IP + 9 * WT) * RP * 2, WT, IP))
+res.sort()
+print("7x7 packs of 4 (worst N-way, staged bytes, WT, IP)", res[:4], "kernel", [r for r in res if r[2:] == (15, 121)])

@@ -1,4 +1,5 @@
-"""Population-batched fp32 ImageNet-shape bottleneck ResNet (v1 / v2) training step: ``--dtype fp32 --model imagenet``.
+"""Population-batched fp32 ImageNet-shape ResNet training step (bottleneck v1 / v2: ResNet-50 ..; v2 building blocks:
+ResNet-18 / 34): ``--dtype fp32 --model imagenet``.
 
 The reference trains in fp32 by default (``resnet/official/utils/flags/_performance.py:30-33``); the bf16 step
 (engine/hip_imagenet.py) is the throughput path.  This one runs the SAME program -- ``_ImageNetPlan``'s v1 / v2
@@ -8,6 +9,8 @@ accumulation in fp32, by overriding the plan's kernel vocabulary:
   convolutions       f32conv.hip generic kernels (v_mfma_f32_16x16x4_f32): 7x7/2 stem on the 4-channel padded
                      input, 1x1 / 3x3 / strided forward with BN-statistic epilogues, transposed-gather data
                      gradients with ReLU-mask + BN-backward-sum epilogues, split-K weight gradients
+  stride-1 3x3       building-block plans: forward and data gradient on f32conv_t3_kernel (whole image rows, the
+                     reduction walked in 16-channel chunks staged in LDS) at the widths of ``_F32_T3``
   dense layer        the same kernels as a 1x1 conv over the GAP features, the class dimension padded to 1024
                      (F32Args.wrows keeps the padding off the 1001-row weight matrix)
   BN apply / sums    f32conv.hip f32_ew (relu(BN), BN-backward apply, v1 relu(BN + shortcut)), f32_bwd_sums
@@ -22,6 +25,7 @@ the bf16 step does.  The step is captured in one HIP graph per batch composition
 from __future__ import annotations
 
 import ctypes
+import os
 
 import torch
 
@@ -31,6 +35,10 @@ from .hip_imagenet import CMAX, NPAD_CLS, GapArgs, HipImageNetBackend, _ImageNet
 from .hip_step import HipBackend, _log2, _p
 
 c_void_p, c_int, c_long = ctypes.c_void_p, ctypes.c_int, ctypes.c_long
+
+# stride-1 3x3 forward / data gradient of the building-block plans on the chunked row-band kernel (f32conv_t3_kernel):
+# the image widths that take it.  DTF_F32_T3=0 (or a width removed from the table) runs the generic kernel there.
+_F32_T3 = {56, 28, 14, 7} if os.environ.get("DTF_F32_T3", "1") == "1" else set()
 
 _REGISTERED = False
 
@@ -48,6 +56,10 @@ def _register():
     ops.register("dtf_f32_softmax_ce", [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_long, c_int, c_void_p,
                                         c_long, c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_void_p])
     ops.register("dtf_f32_gap_args_size", [])
+    ops.register("dtf_f32_conv_t3", [P(F32Args), c_int, c_int, c_int, c_int, c_int, c_void_p])
+    ops.register("dtf_f32_conv_t3_rows", [c_int])
+    ops.register("dtf_f32_conv_t3_pack", [])
+    ops.register("dtf_f32_conv_t3_tc", [])
     L = ops.lib()
     for name, args in ops._SIGNATURES.items():
         fn = getattr(L, name, None)
@@ -60,20 +72,22 @@ def _register():
 
 def supports(arch) -> bool:
     cfg = getattr(arch, "cfg", None)
-    return (cfg is not None and cfg.bottleneck and cfg.version in (1, 2) and cfg.in_channels == 3
+    # bottleneck v1 / v2; building blocks (ResNet-18 / 34) v2 only: the v1 building blocks run on the PyTorch backend
+    return (cfg is not None and cfg.version in ((1, 2) if cfg.bottleneck else (2,)) and cfg.in_channels == 3
             and cfg.first_pool_size == 3 and cfg.first_pool_stride == 2 and cfg.kernel_size == 7
             and cfg.conv_stride == 2 and cfg.image_size % 32 == 0 and cfg.num_classes <= NPAD_CLS)
 
 
 class HipImageNetF32Backend(HipImageNetBackend):
-    """fp32 bottleneck-ResNet step: the bf16 backend's drivers (train_step, eval, infer) over fp32 plans."""
+    """fp32 ImageNet-shape ResNet step: the bf16 backend's drivers (train_step, eval, infer) over fp32 plans."""
 
     accepts_index_batches = False  # index batches are materialised (no in-graph input path for the fp32 step)
 
     def __init__(self, engine):
         _register()
         if not supports(engine.arch):
-            raise ValueError("the fp32 HIP ImageNet backend runs the v1 / v2 bottleneck ImageNet configurations")
+            raise ValueError("the fp32 HIP ImageNet backend runs the v1 / v2 bottleneck and the v2 building-block "
+                             "ImageNet configurations; v1 building blocks run on the torch backend")
         HipBackend.__init__(self, engine)  # (not the bf16 parent's: none of its weight copies are wanted here)
         prog = engine.arch.prog
         self.prog, self.cfg = prog, prog.cfg
@@ -164,7 +178,24 @@ class _ImageNetF32Plan(_ImageNetPlan):
             a = self._f32args(c.off, hw_in, c.cout, c.cout, hw_in * c.stride, c.cin, c.k, c.stride, pad)
         a.x2, a.res, a.xm = _p(x2), _p(res), _p(xm)
         a.c_in, a.c_ep, a.st_out = _p(c_in), _p(c_ep), _p(st)
+        if (self.bb and c.k == 3 and c.stride == 1 and mode == 0 and hw_in in _F32_T3 and not stem
+                and epi in ((6, 7) if dgrad else (4, 5))):
+            self._t3_launch(a, src, out, epi, dgrad)
+            return
         self._conv_launch(a, src, out, mode, epi, dgrad)
+
+    def _t3_launch(self, a, src, out, epi, dgrad):
+        """Stride-1 3x3 forward / data gradient on f32conv_t3_kernel: ``_band_work`` items of whole image rows (packs
+        of whole images at width 7) x the kernel's channel tile."""
+        L = ops.lib()
+        hw = a.Hi
+        assert src.numel() == self.N * hw * hw * a.Ci and out.numel() == self.N * hw * hw * a.Co
+        a.x, a.y = _p(src), _p(out)
+        work = self._band_work(hw, L.dtf_f32_conv_t3_rows(hw), a.Co, L.dtf_f32_conv_t3_tc(),
+                               pack=L.dtf_f32_conv_t3_pack() if hw == 7 else 1)
+        a.work = _p(work)
+        self._hold(a)
+        self._add(L.dtf_f32_conv_t3, ctypes.byref(a), L.dtf_f32_conv_t3_tc(), epi, int(dgrad), hw, work.shape[0])
 
     def wgrad(self, ci, x, dy, hw_in, mode_x=0, c_x=None, mode_dy=0, c_dy=None, dy2=None):
         be = self.be

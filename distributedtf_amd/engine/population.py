@@ -339,7 +339,8 @@ def _half_lib_loaded() -> bool:
 
 def _hip_f32_ok(engine) -> bool:
     """fp32 HIP steps: CIFAR-shape building-block ResNets (engine/hip_f32.py), the MNIST CNN
-    (engine/hip_mnist_f32.py), the ImageNet-shape bottleneck ResNets (engine/hip_imagenet_f32.py)."""
+    (engine/hip_mnist_f32.py), the ImageNet-shape ResNets -- bottleneck v1 / v2 and v2 building blocks
+    (engine/hip_imagenet_f32.py)."""
     if engine.compute_dtype != torch.float32:
         return False
     from .. import ops
@@ -348,8 +349,8 @@ def _hip_f32_ok(engine) -> bool:
     if getattr(engine.arch, "name", "") == "mnist_cnn":
         return True
     from .hip_f32 import supports
-    from .hip_imagenet_f32 import supports as supports_bottleneck
-    return supports(engine.arch) or supports_bottleneck(engine.arch)
+    from .hip_imagenet_f32 import supports as supports_imagenet
+    return supports(engine.arch) or supports_imagenet(engine.arch)
 
 
 def _hip_f16_ok(engine) -> bool:
@@ -380,8 +381,8 @@ def make_backend(engine: PopulationEngine, name: str):
         if getattr(engine.arch, "name", "") == "mnist_cnn":
             from .hip_mnist_f32 import HipMnistF32Backend
             return HipMnistF32Backend(engine)
-        if getattr(getattr(engine.arch, "cfg", None), "bottleneck", False):
-            from .hip_imagenet_f32 import HipImageNetF32Backend
+        from .hip_imagenet_f32 import HipImageNetF32Backend, supports as supports_imagenet
+        if supports_imagenet(engine.arch):  # bottleneck nets and the v2 building-block nets behind the 7x7/2 stem
             return HipImageNetF32Backend(engine)
         from .hip_f32 import HipResNetF32Backend
         return HipResNetF32Backend(engine)

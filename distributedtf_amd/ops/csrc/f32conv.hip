@@ -13,6 +13,8 @@
 //             | A dz + B h + C (BN backward).  Epilogue: [+ residual] [mask by BN(xm) + ReLU > 0] [per-channel
 //             statistics: y, y^2 (forward) or dz, dz * xhat (with the mask)] -> fp32 sums [cap][2][cmax] that the
 //             shared bn_final kernel (convg_aux.hip) turns into coefficients.
+//  f32conv_band / f32conv_t3 : the stride-1 3x3 case from LDS-resident row bands (CIFAR widths, all channels resident;
+//             ImageNet widths, the reduction walked in 16-channel chunks).
 //  f32wgrad : dW[o][k] += sum_p T_dy(dy)[p][o] * T_x(gather(x))[p][k], split over pixel chunks, fp32 atomics into
 //             the member's gradient row.
 //  elementwise / head: BN-backward apply, ReLU(BN) apply, v1 block output and BN-backward sums, global average
@@ -468,6 +470,195 @@ __global__ __launch_bounds__(256) void f32conv_band_kernel(F32Args a) {
         f32_epi4<EPI>(a, slot, pbase + pxl[n], o0 + 16 * m + 4 * j4, true, acc[m][n], ss[m], sq[m]);
   }
   if constexpr (EPI & 4) f32_stats_flush<TCB, (EPI & 2) ? DTF_FX_GRAD : DTF_FX_STAT>(a, slot, o0, ss, sq, acc_lds);
+}
+
+// ---------------------------------------------------------------------------------- chunked row band (ImageNet)
+// Forward or data gradient of a stride-1 3x3 'SAME' conv at the ImageNet widths (56 / 28 / 14 / 7), any Ci, Co that are
+// multiples of 16 (no Ci = Co restriction): the band kernel above keeps ALL channels of its halo tile and a
+// 9 x TCB x (C + 8) weight tile in LDS, which stops at C = 64; this one walks the reduction in chunks of T3_BKC = 16
+// channels.  Work item (slot, p0, p1, o0): R whole rows of one image (4 at 56, 7 at 28, 14 at 14: 224 / 196 pixels)
+// or, at 7, a pack of up to T3_PACK whole consecutive images of one member, times T3_TC = 32 output channels (the last
+// channel tile may be partial: rows past Co read no weights and store nothing).  A ragged pack stages zeros for its
+// missing images and neither stores nor counts them, like the 196-of-208 padding pixels of a 13-tile item.
+// Per chunk: the halo tile ((R + 2) x (W + 2) pixels per image, 16 channels, zero border written by the stager) and
+// the chunk's weights [tap][row][k] are staged once (the data gradient's W[o][t][i] -> [t][i][o] transposed on the
+// way); all 9 taps read their B fragments from the halo tile at a constant offset ((2 - ky, 2 - kx) for the data
+// gradient) from a per-lane base computed once from p -> (image, y, x), so a 16-pixel fragment may wrap across rows
+// and images.  Both operands are read as float4 along k with the k-permutation of the band kernel; pixel and weight-
+// row pitches of 24 floats (8 mod 16) keep the ds_read_b128s conflict-free.  The next chunk's global loads (11 float4
+// per thread) are in flight under the current chunk's 9 x 28 MFMAs per wave.
+// Waves: 2 channel halves (16 rows) x 2 pixel halves (7 pixel tiles): 8 LDS reads per 28 MFMAs.  32-channel tiles keep
+// the workgroup at 61 KB of LDS (56: 33.4 KB halo + 27.6 KB weights), two workgroups per CU and under the 64 KB static
+// limit; a 64-channel tile (55 KB of weights) would leave one.
+constexpr int T3_BKC = 16, T3_TC = 32, T3_PACK = 4;
+constexpr int t3_rows(int w) { return w == 56 ? 4 : (w == 28 ? 7 : (w == 14 ? 14 : (w == 7 ? 7 : 0))); }
+
+// (generated without the compiler's packed fp32 VALU forms, as the later convg.hip instantiations are)
+#ifdef __HIP_DEVICE_COMPILE__
+#define DTF_F32_NO_PK __attribute__((target("no-packed-fp32-ops")))
+#else
+#define DTF_F32_NO_PK
+#endif
+
+// (under that attribute only always_inline callees are inlined: the stager lambdas carry it, and the k loop's barrier
+// is the builtin form of __syncthreads())
+__device__ __forceinline__ void t3_barrier() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+  __builtin_amdgcn_s_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+}
+
+template <int W, int EPI, bool DGRAD>
+__global__ __launch_bounds__(256, 2) DTF_F32_NO_PK void f32conv_t3_kernel(F32Args a) {
+  constexpr int R = t3_rows(W), G = W == 7 ? T3_PACK : 1;
+  constexpr int TC = T3_TC, BKC = T3_BKC;
+  constexpr int IPX = R * W;                  // output pixels per image of the item
+  constexpr int NPX = G * IPX;                // 224 | 196
+  constexpr int NTILE = (NPX + 15) / 16;      // 16-pixel tiles: 14 | 13 (the last one 4 pixels)
+  constexpr int NT = 7;                       // ... per wave
+  constexpr int XW = W + 2, XR = R + 2, XP = BKC + 8, WP = BKC + 8;
+  constexpr int HPX = G * XR * XW;            // halo pixels: 348 | 270 | 256 | 324
+  constexpr int XCH = HPX * (BKC / 4), XQ = (XCH + 255) / 256;
+  constexpr int WCH = 9 * TC * (BKC / 4), WQ = (WCH + 255) / 256;
+  static_assert(R > 0 && W % R == 0 && NTILE <= 2 * NT && NTILE > NT, "t3 geometry");
+  static_assert((HPX * XP + 9 * TC * WP) * 4 + 2 * TC * 8 <= 65536, "t3 LDS");
+  __shared__ __attribute__((aligned(16))) float xL[HPX * XP];
+  __shared__ __attribute__((aligned(16))) float wL[9 * TC * WP];
+  __shared__ dtf_acc_t acc_lds[2][TC];
+  const int4 wk = a.work[blockIdx.x];
+  DTF_WG_CHECK(wk.x >= 0 && wk.y >= 0 && wk.z > wk.y && wk.z - wk.y <= NPX && (wk.z - wk.y) % IPX == 0 &&
+               wk.y % W == 0 && (wk.y / W) % W + R <= W && wk.w >= 0 && wk.w % 16 == 0 && wk.w < a.Co);
+  const int slot = wk.x, p0 = wk.y, p1 = wk.z, o0 = wk.w;
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int j4 = lane >> 4, i16 = lane & 15;
+  const int mh = wave & 1, ph = wave >> 1;    // channel half, pixel half
+  const int Ci = a.Ci, Co = a.Co;
+  const int img0 = p0 / (W * W), y0 = (p0 - img0 * W * W) / W;
+  const int nimg = (p1 - p0) / IPX;
+  for (int i = tid; i < 2 * TC; i += 256) (&acc_lds[0][0])[i] = 0;
+  // ---- this thread's chunks of the halo tile: q = tid + 256 j -> (pixel, 4 channels), constant over the k chunks
+  long xo[XQ];
+  unsigned okx = 0;
+#pragma unroll
+  for (int j = 0; j < XQ; ++j) {
+    const int q = tid + 256 * j;
+    const int pix = q >> 2, c4 = q & 3;
+    const int g = pix / (XR * XW), rem = pix - g * (XR * XW);
+    const int r = rem / XW, c = rem - r * XW;
+    const int iy = y0 - 1 + r, ix = c - 1;
+    const bool ok = q < XCH && g < nimg && iy >= 0 && iy < W && ix >= 0 && ix < W;
+    xo[j] = ((((long)(img0 + g)) * W + iy) * W + ix) * Ci + 4 * c4;
+    okx |= (unsigned)ok << j;
+  }
+  // ---- and of the weight tile: forward (r, t, k4): W[o0 + r][t][k0 + 4 k4 ..]; data gradient (k, t, r4):
+  // W[k0 + k][t][o0 + 4 r4 ..] (the 4 rows of one k: transposed by the store)
+  const float* wrow = a.w + (long)slot * a.w_mstride + a.w_off;
+  int wo[WQ];
+  unsigned okw = 0;
+#pragma unroll
+  for (int j = 0; j < WQ; ++j) {
+    const int q = tid + 256 * j;
+    bool ok;
+    if constexpr (!DGRAD) {
+      const int k4 = q & 3, rt = q >> 2, t = rt % 9, r = rt / 9;
+      ok = q < WCH && o0 + r < Co;
+      wo[j] = ((o0 + r) * 9 + t) * Ci + 4 * k4;
+    } else {
+      const int r4 = q % (TC / 4), kt = q / (TC / 4), t = kt % 9, k = kt / 9;
+      ok = q < WCH && o0 + 4 * r4 < Co;
+      wo[j] = (k * 9 + t) * Co + o0 + 4 * r4;
+    }
+    okw |= (unsigned)ok << j;
+  }
+  float4 rx[XQ], rw[WQ];
+  auto load = [&](int kc) __attribute__((always_inline)) {
+#pragma unroll
+    for (int j = 0; j < XQ; ++j)
+      rx[j] = ((okx >> j) & 1u) ? *reinterpret_cast<const float4*>(a.x + xo[j] + BKC * kc)
+                                : make_float4(0.f, 0.f, 0.f, 0.f);
+    const int wk0 = DGRAD ? BKC * kc * 9 * Co : BKC * kc;
+#pragma unroll
+    for (int j = 0; j < WQ; ++j)
+      rw[j] = ((okw >> j) & 1u) ? *reinterpret_cast<const float4*>(wrow + wo[j] + wk0)
+                                : make_float4(0.f, 0.f, 0.f, 0.f);
+  };
+  auto store = [&]() __attribute__((always_inline)) {
+#pragma unroll
+    for (int j = 0; j < XQ; ++j) {
+      const int q = tid + 256 * j;
+      if (q < XCH) *reinterpret_cast<float4*>(xL + (q >> 2) * XP + 4 * (q & 3)) = rx[j];
+    }
+#pragma unroll
+    for (int j = 0; j < WQ; ++j) {
+      const int q = tid + 256 * j;
+      if (q >= WCH) break;
+      if constexpr (!DGRAD) {
+        const int k4 = q & 3, rt = q >> 2, t = rt % 9, r = rt / 9;
+        *reinterpret_cast<float4*>(wL + (t * TC + r) * WP + 4 * k4) = rw[j];
+      } else {
+        const int r4 = q % (TC / 4), kt = q / (TC / 4), t = kt % 9, k = kt / 9;
+        float* d = wL + (t * TC + 4 * r4) * WP + k;
+        d[0] = rw[j].x, d[WP] = rw[j].y, d[2 * WP] = rw[j].z, d[3 * WP] = rw[j].w;
+      }
+    }
+  };
+  // ---- per-lane pixel of each of the wave's 16-pixel tiles -> its halo-tile base (padding pixels read pixel 0)
+  int xb[NT];
+#pragma unroll
+  for (int n = 0; n < NT; ++n) {
+    int pl = 16 * (NT * ph + n) + i16;
+    if (pl >= NPX) pl = 0;
+    const int g = pl / IPX, rem = pl - g * IPX;
+    const int r = rem / W, c = rem - r * W;
+    xb[n] = ((g * XR + r) * XW + c) * XP + 4 * j4;
+  }
+  f32x4_t acc[NT];
+#pragma unroll
+  for (int n = 0; n < NT; ++n) acc[n] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+  const float* wt0 = wL + (16 * mh + i16) * WP + 4 * j4;
+  const int nc = Ci / BKC;
+  load(0);
+  for (int kc = 0; kc < nc; ++kc) {
+    t3_barrier();  // the previous chunk's tiles are consumed (first chunk: acc_lds zeroed)
+    store();
+    t3_barrier();
+    if (kc + 1 < nc) load(kc + 1);  // the next chunk's loads stay in flight under this chunk's MFMAs
+#pragma unroll
+    for (int t = 0; t < 9; ++t) {
+      const int ky = t / 3, kx = t - 3 * (t / 3);
+      const int boff = DGRAD ? ((2 - ky) * XW + 2 - kx) * XP : (ky * XW + kx) * XP;
+      const float4 av = *reinterpret_cast<const float4*>(wt0 + t * TC * WP);
+#pragma unroll
+      for (int n = 0; n < NT; ++n) {
+        if (NT * ph + n < NTILE) {  // (wave-uniform; the 13-tile items have no tile 13)
+          const float4 bv = *reinterpret_cast<const float4*>(xL + xb[n] + boff);
+          acc[n] = mfma4(av.x, bv.x, acc[n]);
+          acc[n] = mfma4(av.y, bv.y, acc[n]);
+          acc[n] = mfma4(av.z, bv.z, acc[n]);
+          acc[n] = mfma4(av.w, bv.w, acc[n]);
+        }
+      }
+    }
+  }
+  // ---- epilogue: lane holds channels o0 + 16 mh + 4 j4 + i of pixel p0 + 16 (NT ph + n) + i16
+  float s1[4] = {0.f, 0.f, 0.f, 0.f}, q1[4] = {0.f, 0.f, 0.f, 0.f};
+  const int co = o0 + 16 * mh + 4 * j4;
+#pragma unroll
+  for (int n = 0; n < NT; ++n) {
+    const int p = p0 + 16 * (NT * ph + n) + i16;
+    f32_epi4<EPI>(a, slot, p, co, p < p1 && co < Co, acc[n], s1, q1);
+  }
+  if constexpr (EPI & 4) {
+    float ss[TC / 16][4], sq[TC / 16][4];  // the shared flush takes every row tile: the other half's are zero
+#pragma unroll
+    for (int m = 0; m < TC / 16; ++m)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        ss[m][i] = m == mh ? s1[i] : 0.f;
+        sq[m][i] = m == mh ? q1[i] : 0.f;
+      }
+    f32_stats_flush<TC, (EPI & 2) ? DTF_FX_GRAD : DTF_FX_STAT>(a, slot, o0, ss, sq, acc_lds);
+  }
 }
 
 // ------------------------------------------------------------------------------------------------------ wgrad
@@ -1125,6 +1316,35 @@ DTF_API int dtf_f32_conv_band(const F32Args* a, int mode, int epi, int dgrad, in
   CB_CWS(2, 0, true)
 #undef CB_CWS
 #undef CB_CASE
+  return -1;
+}
+
+// chunked row-band fwd / dgrad of a stride-1 3x3 'SAME' conv on w x w images, w in 56 / 28 / 14 / 7 (f32conv_t3_kernel):
+// work rows (slot, p0, p1, o0) of dtf_f32_conv_t3_rows(w) whole image rows (at 7: up to dtf_f32_conv_t3_pack() whole
+// images of one member) x tc = dtf_f32_conv_t3_tc() output channels; operand as stored (MODE 0); epi 4 / 5 (forward:
+// statistics [+ residual]) or 6 / 7 (data gradient: mask + BN-backward sums [+ residual]).
+DTF_API int dtf_f32_conv_t3_rows(int w) { return t3_rows(w); }
+DTF_API int dtf_f32_conv_t3_pack() { return T3_PACK; }
+DTF_API int dtf_f32_conv_t3_tc() { return T3_TC; }
+
+DTF_API int dtf_f32_conv_t3(const F32Args* a, int tc, int epi, int dgrad, int w, int nwork, hipStream_t stream) {
+  if (nwork <= 0) return 0;
+  if (a->kh != 3 || a->kw != 3 || a->stride != 1 || a->pad != 1 || a->Hi != w || a->Wi != w || a->Ho != w ||
+      a->Wo != w || a->Ci <= 0 || a->Ci % 16 != 0 || a->Co <= 0 || a->Co % 16 != 0 || a->wci != a->Ci ||
+      a->wrows != 0 || (a->w_off & 3) != 0 || (a->w_mstride & 3) != 0)
+    return -2;
+  DTF_HOST_CHECK(DTF_ALIGNED16(a->x) && DTF_ALIGNED16(a->y) && DTF_ALIGNED16(a->w) && a->work && a->st_out);
+  DTF_HOST_CHECK(!(epi & 1) || DTF_ALIGNED16(a->res));
+  DTF_HOST_CHECK(!(epi & 2) || (DTF_ALIGNED16(a->xm) && a->c_ep));
+#define T3_CASE(W_, E_, D_)                                                                              \
+  if (tc == T3_TC && w == W_ && epi == E_ && dgrad == D_) {                                              \
+    hipLaunchKernelGGL((f32conv_t3_kernel<W_, E_, D_>), dim3(nwork), dim3(256), 0, stream, *a);          \
+    return DTF_CHECK_LAUNCH();                                                                           \
+  }
+#define T3_WS(E_, D_) T3_CASE(56, E_, D_) T3_CASE(28, E_, D_) T3_CASE(14, E_, D_) T3_CASE(7, E_, D_)
+  T3_WS(4, false) T3_WS(5, false) T3_WS(6, true) T3_WS(7, true)
+#undef T3_WS
+#undef T3_CASE
   return -1;
 }
 

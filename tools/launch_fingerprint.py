@@ -263,6 +263,9 @@ def sections(dev):
         arch = ResNetArch(imagenet_config(18, 2, num_classes=1001, image_size=image))
         be = hip_imagenet.HipImageNetBackend(engine(arch, 2, dev, d16, **kw16))
         yield from plans("imagenet18 v2 image %d" % image, be, [([0, 1], [5, 1])], [([0, 1], 2)])
+        if not half:  # fp32: the chunked row-band kernel at 224
+            be = hip_imagenet_f32.HipImageNetF32Backend(engine(arch, 2, dev, torch.float32))
+            yield from plans("imagenet18 v2 image %d fp32" % image, be, [([0, 1], [5, 1])], [([0, 1], 2)])
 
 
 def main():

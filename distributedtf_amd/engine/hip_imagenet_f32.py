@@ -10,7 +10,9 @@ accumulation in fp32, by overriding the plan's kernel vocabulary:
                      input, 1x1 / 3x3 / strided forward with BN-statistic epilogues, transposed-gather data
                      gradients with ReLU-mask + BN-backward-sum epilogues, split-K weight gradients
   stride-1 3x3       building-block plans: forward and data gradient on f32conv_t3_kernel (whole image rows, the
-                     reduction walked in 16-channel chunks staged in LDS) at the widths of ``_F32_T3``
+                     reduction walked in 16-channel chunks staged in LDS) at the widths of ``_F32_T3``; weight
+                     gradient on f32wgrad_t3_kernel (row bands of dy and the halo tile of x staged once for all 9
+                     taps, a 64-row x 16-channel tile of dW per item) at the widths of ``_F32_WGT3``
   dense layer        the same kernels as a 1x1 conv over the GAP features, the class dimension padded to 1024
                      (F32Args.wrows keeps the padding off the 1001-row weight matrix)
   BN apply / sums    f32conv.hip f32_ew (relu(BN), BN-backward apply, v1 relu(BN + shortcut)), f32_bwd_sums
@@ -39,6 +41,12 @@ c_void_p, c_int, c_long = ctypes.c_void_p, ctypes.c_int, ctypes.c_long
 # stride-1 3x3 forward / data gradient of the building-block plans on the chunked row-band kernel (f32conv_t3_kernel):
 # the image widths that take it.  DTF_F32_T3=0 (or a width removed from the table) runs the generic kernel there.
 _F32_T3 = {56, 28, 14, 7} if os.environ.get("DTF_F32_T3", "1") == "1" else set()
+# ... and their weight gradients on the row-band kernel (f32wgrad_t3_kernel); DTF_F32_WGT3=0 runs the generic split-K
+# kernel there.  Each member's bands are split into runs so that a launch has about _F32_WGT3_TARGET items: 512 and 1024
+# measure the same (37.27 / 37.26 ms per ResNet-18 step, 66.67 / 66.68 per ResNet-34 step), 256 is 0.5 - 0.9 ms slower;
+# removing any one width costs 0.55 - 2.4 ms against a spread below 0.25 ms (profiles/f32_wgt3_ab.txt).
+_F32_WGT3 = {56, 28, 14, 7} if os.environ.get("DTF_F32_WGT3", "1") == "1" else set()
+_F32_WGT3_TARGET = 512
 
 _REGISTERED = False
 
@@ -60,6 +68,10 @@ def _register():
     ops.register("dtf_f32_conv_t3_rows", [c_int])
     ops.register("dtf_f32_conv_t3_pack", [])
     ops.register("dtf_f32_conv_t3_tc", [])
+    ops.register("dtf_f32_wgrad_t3", [P(F32Args), c_int, c_int, c_void_p])
+    ops.register("dtf_f32_wgrad_t3_rows", [c_int])
+    for q in ("pack", "to", "ti"):
+        ops.register("dtf_f32_wgrad_t3_" + q, [])
     L = ops.lib()
     for name, args in ops._SIGNATURES.items():
         fn = getattr(L, name, None)
@@ -204,7 +216,35 @@ class _ImageNetF32Plan(_ImageNetPlan):
         hw_out = (hw_in + c.stride - 1) // c.stride
         a = self._f32args(c.off, hw_in, 4 if stem else c.cin, c.cin, hw_out, c.cout, c.k, c.stride, (c.k - 1) // 2)
         a.dy, a.dy2, a.c_in, a.c_dy = _p(dy), _p(dy2), _p(c_x), _p(c_dy)
+        if (self.bb and c.k == 3 and c.stride == 1 and not stem and mode_x == 0 and mode_dy == 0
+                and hw_in in _F32_WGT3):
+            self._wgrad_t3_launch(a, x, hw_in)
+            return
         self._wgrad_launch(a, x, mode_x, mode_dy)
+
+    def _wgrad_t3_launch(self, a, x, hw):
+        """Stride-1 3x3 weight gradient on f32wgrad_t3_kernel: items (slot, first band, end band, o0 | ci chunk << 16)
+        -- per member, per output-row tile and input-channel chunk of the kernel, the member's bands (width 7: its
+        images, in whole packs) split into runs so that the launch has about _F32_WGT3_TARGET items."""
+        L = ops.lib()
+        assert x.numel() == self.N * hw * hw * a.Ci
+        a.x = _p(x)
+        bpi = hw // L.dtf_f32_wgrad_t3_rows(hw)
+        pack = L.dtf_f32_wgrad_t3_pack() if hw == 7 else 1
+        tiles = [o0 | (cc << 16) for o0 in range(0, a.Co, L.dtf_f32_wgrad_t3_to())
+                 for cc in range(a.Ci // L.dtf_f32_wgrad_t3_ti())]
+        total = sum(self.sizes) * bpi * len(tiles)
+        chunk = -(-max(1, -(-total // _F32_WGT3_TARGET)) // pack) * pack
+        items = []
+        for s, n in zip(self.slots, self.sizes):
+            f = self.first[s]
+            for b in range(f * bpi, (f + n) * bpi, chunk):
+                items += [[s, b, min(b + chunk, (f + n) * bpi), t] for t in tiles]
+        items = self._xcd_order(items, len(tiles))
+        work = self._hold(torch.tensor(items, dtype=torch.int32, device=self.be.dev))
+        a.work = _p(work)
+        self._hold(a)
+        self._add(L.dtf_f32_wgrad_t3, ctypes.byref(a), hw, work.shape[0])
 
     def _wgrad_launch(self, a, x, mode_x, mode_dy):
         N = self.N

@@ -17,6 +17,8 @@
 //             ImageNet widths, the reduction walked in 16-channel chunks).
 //  f32wgrad : dW[o][k] += sum_p T_dy(dy)[p][o] * T_x(gather(x))[p][k], split over pixel chunks, fp32 atomics into
 //             the member's gradient row.
+//  f32wgrad_band / f32wgrad_t3 : the stride-1 3x3 weight gradient from LDS-resident row bands (CIFAR widths, all
+//             channels resident; ImageNet widths, a 64-row x 16-channel tile of dW per item).
 //  elementwise / head: BN-backward apply, ReLU(BN) apply, v1 block output and BN-backward sums, global average
 //             pool (+ final BN + ReLU), dense + softmax CE, dense gradient (fixed-order per member), GAP backward.
 #include "common.h"
@@ -976,6 +978,152 @@ __global__ __launch_bounds__(256) void f32wgrad_band_kernel(F32Args a) {
   }
 }
 
+// --------------------------------------------------------------------------- chunked row-band wgrad (ImageNet)
+// Weight gradient of a stride-1 3x3 'SAME' conv at the ImageNet widths (56 / 28 / 14 / 7), any Ci, Co that are multiples
+// of 16, plain operands: dW[o][ky][kx][ci] += sum_p dy[p][o] x[p + (ky - 1, kx - 1)][ci].  The band kernel above keeps
+// all C channels of dy in LDS and needs Ci = Co = C <= 64; this one takes a WT3_TO = 64-row output tile (the last one
+// may be partial) and a WT3_TI = 16-channel input chunk per item, so any channel count fits the same 51 KB.
+// Work item (slot, first band, end band, o0 | ci chunk << 16): a run of bands of ONE member.  Band b = image b / BPI,
+// rows (b % BPI) R .. (R = 2 at 56, 4 at 28, 7 at 14: 112 / 112 / 98 pixels); at width 7 the unit is a whole image
+// (BPI = 1) and the run is walked WT3_PACK = 2 images at a time, the last pack of an odd run holding one image.
+// Per band the workgroup stages once
+//   xL: the halo tile, (R + 2) x (W + 2) pixels per image x 16 channels, pitch 16 floats -- the four lane / 16 groups
+//       of a B fragment read four consecutive pixels, 64 consecutive words;
+//   dL: the band of dy, NPX4 pixels x 64 channels at pitch f_pitch(64) = 80 -- the four groups of an A fragment read
+//       land 16 banks apart;
+// and each wave (16 output rows, all 9 taps: 9 accumulator tiles that live across the whole run) walks the band in
+// groups of 4 pixels: 1 A read (dy^T: 16 o x 4 pixels) + 9 B reads (x at the tap's constant offset from the per-lane
+// base xb[g], computed once from p -> (image, y, x), so a group may wrap across rows and images) per 9 MFMAs, no
+// cross-wave reduction.  The next band's global loads (4 + 7 float4 per thread) stay in registers, in flight under
+// the current band's MFMAs.  One add per weight and item.
+//
+// Unlike the forward no epilogue drops anything here: every product is summed, so whatever is not data must be ZERO
+// IN BOTH operands (0 * NaN is NaN), and every LDS word an MFMA reads must have been written:
+//  * A fragments read dL[p][16 wave + lane % 16], p < NPX4, columns 0 .. 63 (the pitch padding is never read).
+//    store() writes all NPX4 x 16 float4 of that range every band; load() zeroes pixels past the band's images
+//    (p >= nimg * IPX: the ragged pack, and the 2 pixels that round 98 up to 100) and channels past Co.
+//  * B fragments read xL[xb[g] + tap offset + lane % 16].  For p < NPX the base is halo pixel (image g, r, c) and the
+//    offset adds (ky, kx) <= (2, 2): pixel (r + ky, c + kx) <= (R + 1, W + 1) of the same image's tile.  store()
+//    writes all HPX x 4 float4 of the tile every band; load() zeroes the border columns, rows outside the image
+//    and images past the pack's.  For p >= NPX the base is the first of ZPX = 2 (W + 2) + 3 zero pixels behind the
+//    tile, written once before the first barrier: base + offset stays inside them.
+// A wave whose 16 rows lie past Co (partial last tile) runs no MFMA and adds nothing.
+constexpr int WT3_TO = 64, WT3_TI = 16, WT3_PACK = 2;
+constexpr int wt3_rows(int w) { return w == 56 ? 2 : (w == 28 ? 4 : (w == 14 ? 7 : (w == 7 ? 7 : 0))); }
+
+template <int W>
+__global__ __launch_bounds__(256) void f32wgrad_t3_kernel(F32Args a) {
+  constexpr int R = wt3_rows(W), G = W == 7 ? WT3_PACK : 1, BPI = W / R;
+  constexpr int TO = WT3_TO, TI = WT3_TI;
+  constexpr int IPX = R * W, NPX = G * IPX;          // pixels per image of a band; per band: 112 | 98
+  constexpr int NG = (NPX + 3) / 4, NPX4 = 4 * NG;   // 4-pixel groups: 28 | 25
+  constexpr int XW = W + 2, XR = R + 2, XP = TI, DP = f_pitch(TO);
+  constexpr int HPX = G * XR * XW;                   // halo pixels: 232 | 180 | 144 | 162
+  constexpr int ZPX = NPX4 > NPX ? 2 * XW + 3 : 0;   // zero pixels behind the tile (the padding pixels' B operand)
+  constexpr int XCH = HPX * (TI / 4), XQ = (XCH + 255) / 256;
+  constexpr int DCH = NPX4 * (TO / 4), DQ = (DCH + 255) / 256;
+  static_assert(R > 0 && W % R == 0 && (G == 1 || BPI == 1) && TI == 16 && TO == 64, "wgrad t3 geometry");
+  static_assert(((HPX + ZPX) * XP + NPX4 * DP) * 4 <= 65536, "wgrad t3 LDS");
+  __shared__ __attribute__((aligned(16))) float xL[(HPX + ZPX) * XP];
+  __shared__ __attribute__((aligned(16))) float dL[NPX4 * DP];
+  const int4 wk = a.work[blockIdx.x];
+  DTF_WG_CHECK(wk.x >= 0 && wk.y >= 0 && wk.z > wk.y && (wk.w & 0xffff) % 16 == 0 && (wk.w & 0xffff) < a.Co &&
+               (wk.w >> 16) >= 0 && ((wk.w >> 16) + 1) * TI <= a.Ci);
+  const int slot = wk.x, b0 = wk.y, b1 = wk.z, o0 = wk.w & 0xffff, c0 = (wk.w >> 16) * TI;
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int j4 = lane >> 4, i16 = lane & 15;
+  const int Ci = a.Ci, Co = a.Co;
+  for (int i = tid; i < ZPX * XP; i += 256) xL[HPX * XP + i] = 0.f;
+  // ---- this thread's chunks of the halo tile: q = tid + 256 j -> (image of the pack, row - 1, column - 1, 4 channels)
+  // relative to the band's first row; row validity depends on the band
+  int xrel[XQ], xrow[XQ], ximg[XQ];
+  unsigned okc = 0;
+#pragma unroll
+  for (int j = 0; j < XQ; ++j) {
+    const int q = tid + 256 * j;
+    const int pix = q >> 2, c4 = q & 3;
+    const int g = pix / (XR * XW), rem = pix - g * (XR * XW);
+    const int r = rem / XW, c = rem - r * XW;
+    xrow[j] = r - 1;
+    ximg[j] = g;
+    xrel[j] = ((g * W + r - 1) * W + c - 1) * Ci + c0 + 4 * c4;
+    okc |= (unsigned)(q < XCH && c >= 1 && c <= W) << j;
+  }
+  float4 rx[XQ], rd[DQ];
+  auto load = [&](int b) {
+    const int img0 = b / BPI, y0 = (b - img0 * BPI) * R;
+    const int nimg = b1 - b < G ? b1 - b : G;
+    const float* xb_ = a.x + ((long)img0 * W + y0) * W * Ci;
+#pragma unroll
+    for (int j = 0; j < XQ; ++j) {
+      const int iy = y0 + xrow[j];
+      const bool ok = ((okc >> j) & 1u) && iy >= 0 && iy < W && ximg[j] < nimg;
+      rx[j] = ok ? *reinterpret_cast<const float4*>(xb_ + xrel[j]) : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    const float* db = a.dy + ((long)img0 * W + y0) * W * Co + o0;  // the band's pixels are contiguous in NHWC
+#pragma unroll
+    for (int j = 0; j < DQ; ++j) {
+      const int q = tid + 256 * j;
+      const int pix = q >> 4, oc = 4 * (q & 15);
+      const bool ok = q < DCH && pix < nimg * IPX && o0 + oc < Co;
+      rd[j] = ok ? *reinterpret_cast<const float4*>(db + (long)pix * Co + oc) : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+  };
+  auto store = [&]() {
+#pragma unroll
+    for (int j = 0; j < XQ; ++j) {
+      const int q = tid + 256 * j;
+      if (q < XCH) *reinterpret_cast<float4*>(xL + (q >> 2) * XP + 4 * (q & 3)) = rx[j];
+    }
+#pragma unroll
+    for (int j = 0; j < DQ; ++j) {
+      const int q = tid + 256 * j;
+      if (q < DCH) *reinterpret_cast<float4*>(dL + (q >> 4) * DP + 4 * (q & 15)) = rd[j];
+    }
+  };
+  // ---- per-lane pixel of each 4-pixel group -> its halo-tile base (padding pixels: the zero pixels)
+  int xb[NG];
+#pragma unroll
+  for (int g = 0; g < NG; ++g) {
+    const int p = 4 * g + j4;
+    const int gi = p / IPX, rem = p - gi * IPX;
+    const int r = rem / W, c = rem - r * W;
+    xb[g] = (p < NPX ? (gi * XR + r) * XW + c : HPX) * XP + i16;
+  }
+  f32x4_t acc[9];
+#pragma unroll
+  for (int t = 0; t < 9; ++t) acc[t] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+  const bool live = o0 + 16 * wave < Co;  // (wave-uniform: Co % 16 == 0)
+  const float* dl = dL + j4 * DP + 16 * wave + i16;
+  load(b0);
+  for (int b = b0; b < b1; b += G) {
+    __syncthreads();  // the previous band's tiles are consumed (first band: the zero pixels are written)
+    store();
+    __syncthreads();
+    if (b + G < b1) load(b + G);  // the next band's loads stay in flight under this band's MFMAs
+    if (live) {
+#pragma unroll
+      for (int g = 0; g < NG; ++g) {
+        const float av = dl[4 * g * DP];
+#pragma unroll
+        for (int t = 0; t < 9; ++t)
+          acc[t] = mfma4(av, xL[xb[g] + ((t / 3) * XW + t % 3) * XP], acc[t]);
+      }
+    }
+  }
+  // ---- lane holds dW[o0 + 16 wave + 4 j4 + i][tap][c0 + i16]
+  if (live) {
+    dtf_acc_t* g = reinterpret_cast<dtf_acc_t*>(a.grads) + (long)slot * a.g_mstride + a.g_off;
+#pragma unroll
+    for (int t = 0; t < 9; ++t)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int o = o0 + 16 * wave + 4 * j4 + i;
+        dtf_acc_add(g + ((long)o * 9 + t) * Ci + c0 + i16, acc[t][i], DTF_FX_GRAD, slot);
+      }
+  }
+}
+
 // ------------------------------------------------------------------------------------------------ elementwise
 struct F32Ew {
   const float* dz;
@@ -1369,6 +1517,32 @@ DTF_API int dtf_f32_wgrad_band(const F32Args* a, int mode_x, int mode_dy, int nw
 
 DTF_API int dtf_f32_wgrad_band_ok(int C, int W) {
   return (C == 16 && W == 32) || (C == 32 && W == 16) || (C == 64 && W == 8);
+}
+
+// chunked row-band wgrad of a stride-1 3x3 'SAME' conv on w x w images, w in 56 / 28 / 14 / 7 (f32wgrad_t3_kernel),
+// plain operands: work rows (slot, first band, end band, o0 | ci chunk << 16) over bands of dtf_f32_wgrad_t3_rows(w)
+// image rows (at 7: whole images, staged dtf_f32_wgrad_t3_pack() at a time), dtf_f32_wgrad_t3_to() output rows and
+// dtf_f32_wgrad_t3_ti() input channels.
+DTF_API int dtf_f32_wgrad_t3_rows(int w) { return wt3_rows(w); }
+DTF_API int dtf_f32_wgrad_t3_pack() { return WT3_PACK; }
+DTF_API int dtf_f32_wgrad_t3_to() { return WT3_TO; }
+DTF_API int dtf_f32_wgrad_t3_ti() { return WT3_TI; }
+
+DTF_API int dtf_f32_wgrad_t3(const F32Args* a, int w, int nwork, hipStream_t stream) {
+  if (nwork <= 0) return 0;
+  if (a->kh != 3 || a->kw != 3 || a->stride != 1 || a->pad != 1 || a->Hi != w || a->Wi != w || a->Ho != w ||
+      a->Wo != w || a->Ci <= 0 || a->Ci % 16 != 0 || a->Co <= 0 || a->Co % 16 != 0 || a->wci != a->Ci ||
+      a->wrows != 0 || (a->g_off & 3) != 0 || (a->g_mstride & 3) != 0)
+    return -2;
+  DTF_HOST_CHECK(DTF_ALIGNED16(a->x) && DTF_ALIGNED16(a->dy) && a->grads && a->work);
+#define WT3_CASE(W_)                                                                                     \
+  if (w == W_) {                                                                                         \
+    hipLaunchKernelGGL((f32wgrad_t3_kernel<W_>), dim3(nwork), dim3(256), 0, stream, *a);                 \
+    return DTF_CHECK_LAUNCH();                                                                           \
+  }
+  WT3_CASE(56) WT3_CASE(28) WT3_CASE(14) WT3_CASE(7)
+#undef WT3_CASE
+  return -1;
 }
 
 DTF_API int dtf_f32_ew(const F32Ew* a, int which, hipStream_t stream) {

@@ -13,6 +13,9 @@ accumulation in fp32, by overriding the plan's kernel vocabulary:
                      reduction walked in 16-channel chunks staged in LDS) at the widths of ``_F32_T3``; weight
                      gradient on f32wgrad_t3_kernel (row bands of dy and the halo tile of x staged once for all 9
                      taps, a 64-row x 16-channel tile of dW per item) at the widths of ``_F32_WGT3``
+  stride-1 1x1       every plan: forward and data gradient on f32conv_pw_kernel (a GEMM over flat pixel ranges of one
+                     member, 128 x 128 or, for outputs of at most 64 channels, 64 x 256 tiles) unless ``_F32_PW`` is off;
+                     data gradients with a reduction below ``_F32_PW_DGRAD_MIN_K`` channels keep the generic kernel
   dense layer        the same kernels as a 1x1 conv over the GAP features, the class dimension padded to 1024
                      (F32Args.wrows keeps the padding off the 1001-row weight matrix)
   BN apply / sums    f32conv.hip f32_ew (relu(BN), BN-backward apply, v1 relu(BN + shortcut)), f32_bwd_sums
@@ -47,6 +50,14 @@ _F32_T3 = {56, 28, 14, 7} if os.environ.get("DTF_F32_T3", "1") == "1" else set()
 # removing any one width costs 0.55 - 2.4 ms against a spread below 0.25 ms (profiles/f32_wgt3_ab.txt).
 _F32_WGT3 = {56, 28, 14, 7} if os.environ.get("DTF_F32_WGT3", "1") == "1" else set()
 _F32_WGT3_TARGET = 512
+# stride-1 1x1 forward / data gradient (plain operand) on the pointwise kernel (f32conv_pw_kernel); DTF_F32_PW=0 runs
+# the generic kernel there (the launch lists of before the kernel existed).
+_F32_PW = os.environ.get("DTF_F32_PW", "1") == "1"
+_F32_PW_EPI = {False: (0, 4, 5), True: (0, 3, 6, 7)}  # the instantiated epilogues by direction (dgrad)
+# data gradients with a reduction (the forward conv's output channels) shorter than this stay on the generic kernel:
+# at 64 and 128 the pointwise kernel measured 6 - 17 % slower per launch there (267 vs 230, 758 vs 655, 1114 vs 960,
+# 479 vs 451 us), from 256 up 6 - 33 % faster; every forward class is faster (profiles/f32_pw_ab.txt)
+_F32_PW_DGRAD_MIN_K = 256
 
 _REGISTERED = False
 
@@ -68,6 +79,9 @@ def _register():
     ops.register("dtf_f32_conv_t3_rows", [c_int])
     ops.register("dtf_f32_conv_t3_pack", [])
     ops.register("dtf_f32_conv_t3_tc", [])
+    ops.register("dtf_f32_conv_pw", [P(F32Args), c_int, c_int, c_int, c_int, c_void_p])
+    ops.register("dtf_f32_conv_pw_tc", [c_int])
+    ops.register("dtf_f32_conv_pw_tp", [c_int])
     ops.register("dtf_f32_wgrad_t3", [P(F32Args), c_int, c_int, c_void_p])
     ops.register("dtf_f32_wgrad_t3_rows", [c_int])
     for q in ("pack", "to", "ti"):
@@ -194,7 +208,39 @@ class _ImageNetF32Plan(_ImageNetPlan):
                 and epi in ((6, 7) if dgrad else (4, 5))):
             self._t3_launch(a, src, out, epi, dgrad)
             return
+        if (_F32_PW and c.k == 1 and c.stride == 1 and mode == 0 and not stem and a.Ci % 16 == 0 and a.Co % 16 == 0
+                and epi in _F32_PW_EPI[bool(dgrad)] and (not dgrad or a.Ci >= _F32_PW_DGRAD_MIN_K)):
+            self._pw_launch(a, src, out, epi, dgrad)
+            return
         self._conv_launch(a, src, out, mode, epi, dgrad)
+
+    def _pw_launch(self, a, src, out, epi, dgrad):
+        """Stride-1 1x1 forward / data gradient on f32conv_pw_kernel: items (slot, p0, p1, o0) of flat pixel ranges of
+        one member x the channel tile -- the library's narrowest tile that holds all of Co, else its widest."""
+        L = ops.lib()
+        hw2 = a.Hi * a.Wi
+        assert src.numel() == self.N * hw2 * a.Ci and out.numel() == self.N * hw2 * a.Co
+        a.x, a.y = _p(src), _p(out)
+        tcs = []
+        while L.dtf_f32_conv_pw_tc(len(tcs)) > 0:
+            tcs.append(L.dtf_f32_conv_pw_tc(len(tcs)))
+        tc = min([t for t in tcs if t >= a.Co] or [max(tcs)])
+        work = self._pw_work(hw2, a.Co, tc, L.dtf_f32_conv_pw_tp(tc))
+        a.work = _p(work)
+        self._hold(a)
+        self._add(L.dtf_f32_conv_pw, ctypes.byref(a), tc, epi, int(dgrad), work.shape[0])
+
+    def _pw_work(self, hw2, co, tc, tp):
+        """(slot, p0, p1, o0) tiles of up to tp consecutive pixels of one member (images of hw2 pixels; the ranges
+        ignore the image boundaries, the last one of a member is ragged) x tc output channels."""
+        items = []
+        for s, n in zip(self.slots, self.sizes):
+            f = self.first[s]
+            for p0 in range(f * hw2, (f + n) * hw2, tp):
+                for o0 in range(0, co, tc):
+                    items.append([s, p0, min(p0 + tp, (f + n) * hw2), o0])
+        items = self._xcd_order(items, -(-co // tc))
+        return self._hold(torch.tensor(items, dtype=torch.int32, device=self.be.dev))
 
     def _t3_launch(self, a, src, out, epi, dgrad):
         """Stride-1 3x3 forward / data gradient on f32conv_t3_kernel: ``_band_work`` items of whole image rows (packs

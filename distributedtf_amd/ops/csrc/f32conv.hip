@@ -102,9 +102,10 @@ __device__ __forceinline__ void f32_epi4(const F32Args& a, int slot, long p, int
 
 // Workgroup statistics: the 16 lanes of one lane / 16 group hold the same 4 channels -- butterfly, one LDS atomic
 // per group and channel, one global atomic per workgroup and channel.  acc_lds [2][TC] zeroed before the k loop.
+// ss / sq hold the caller's row tiles m0 .. m0 + MT of the TC / 16 (a wave that owns a part of the channel tile).
 template <int TC, int FX, int MT>
 __device__ __forceinline__ void f32_stats_flush(const F32Args& a, int slot, int o0, float (&ss)[MT][4],
-                                                float (&sq)[MT][4], dtf_acc_t (&acc_lds)[2][TC]) {
+                                                float (&sq)[MT][4], dtf_acc_t (&acc_lds)[2][TC], int m0 = 0) {
   const int tid = threadIdx.x, lane = tid & 63;
 #pragma unroll
   for (int m = 0; m < MT; ++m)
@@ -117,8 +118,8 @@ __device__ __forceinline__ void f32_stats_flush(const F32Args& a, int slot, int 
         q_ += __shfl_xor(q_, o, 64);
       }
       if ((lane & 15) == 0) {
-        dtf_acc_add(&acc_lds[0][16 * m + 4 * (lane >> 4) + i], s_, FX, slot);
-        dtf_acc_add(&acc_lds[1][16 * m + 4 * (lane >> 4) + i], q_, FX, slot);
+        dtf_acc_add(&acc_lds[0][16 * (m0 + m) + 4 * (lane >> 4) + i], s_, FX, slot);
+        dtf_acc_add(&acc_lds[1][16 * (m0 + m) + 4 * (lane >> 4) + i], q_, FX, slot);
       }
     }
   __syncthreads();
@@ -661,6 +662,152 @@ __global__ __launch_bounds__(256, 2) DTF_F32_NO_PK void f32conv_t3_kernel(F32Arg
       }
     f32_stats_flush<TC, (EPI & 2) ? DTF_FX_GRAD : DTF_FX_STAT>(a, slot, o0, ss, sq, acc_lds);
   }
+}
+
+// ------------------------------------------------------------------------------------- pointwise fwd / dgrad
+// Forward or data gradient of a stride-1 1x1 conv (the bottleneck nets' conv1 / conv3 / stage-1 projection): a plain
+// GEMM over a flat pixel range, out[p][o] = sum_c W[o][c] x[p][c] (data gradient: dx[p][i] = sum_o W[o][i] dy[p][o]),
+// any Ci, Co that are multiples of 16, plain operand.  Work item (slot, p0, p1, o0): up to TP consecutive pixels of one
+// member (ragged tail allowed; image boundaries mean nothing here, so there is no p -> (image, y, x) arithmetic) times
+// TC output channels from o0 (the last channel tile may be partial).  Two forms: TC x TP = 128 x 128, and 64 x 256 for
+// narrow outputs; the 4 waves split the tile 2 (channel halves) x 2 (pixel halves), so a wave owns 64 x 64 or 32 x 128:
+// 16 accumulator tiles either way.
+// The reduction is walked in chunks of PW_BKC = 16 channels.  Both operands are contiguous along k in memory (the
+// weight row W[o][k0 ..] and the pixel x[p][k0 ..]), so a chunk is staged as [row][k] with float4 global loads and float4
+// LDS stores, no transposition; the data gradient's weight operand W[k][o0 ..] is contiguous along its rows instead and
+// is transposed by the store (lanes walk k fastest: a 2-way bank conflict on 4 ds_write_b32).  Row pitch 24 floats (8
+// mod 16): every fragment is a conflict-free ds_read_b128 along k with the k-permutation of the band kernels (lane l
+// takes k = 4 (l / 16) .. + 3, MFMA q of the four uses element q, A and B alike).  Per chunk a wave issues MT + NT = 8
+// (10 in the narrow form) reads for 64 MFMAs.  The next chunk's global loads (4 / 5 float4 per thread) stay in
+// registers under the current chunk's MFMAs; one LDS buffer, a barrier on either side of the store.
+// Padding: rows past Co and pixels past p1 are staged as ZEROS in every chunk, and the fragment reads touch floats
+// 0 .. 15 of a row only (the 8 pitch floats are never read), so every LDS word an MFMA reads has been written; the
+// epilogue stores and counts nothing for those rows and pixels.
+constexpr int PW_BKC = 16, PW_NTC = 2;
+constexpr int pw_tc(int i) { return i == 0 ? 128 : (i == 1 ? 64 : 0); }
+constexpr int pw_tp(int tc) { return tc == 128 ? 128 : (tc == 64 ? 256 : 0); }
+
+template <int TC, int TP, int EPI, bool DGRAD>
+__global__ __launch_bounds__(256, 2) DTF_F32_NO_PK void f32conv_pw_kernel(F32Args a) {
+  constexpr int BKC = PW_BKC, P = BKC + 8;
+  constexpr int MT = TC / 32, NT = TP / 32;   // 16 x 16 tiles per wave: rows (channels), columns (pixels)
+  constexpr int AQ = TC * (BKC / 4) / 256, BQ = TP * (BKC / 4) / 256;  // float4 chunks per thread and stage
+  static_assert(MT * NT == 16 && AQ >= 1 && BQ >= 1 && TC % 64 == 0 && TP % 64 == 0, "pw geometry");
+  static_assert((TC + TP) * P * 4 + 2 * TC * 8 <= 65536, "pw LDS");
+  __shared__ __attribute__((aligned(16))) float wL[TC * P];
+  __shared__ __attribute__((aligned(16))) float xL[TP * P];
+  __shared__ dtf_acc_t acc_lds[2][TC];
+  const int4 wk = a.work[blockIdx.x];
+  DTF_WG_CHECK(wk.x >= 0 && wk.y >= 0 && wk.z > wk.y && wk.z - wk.y <= TP && wk.w >= 0 && wk.w % 16 == 0 &&
+               wk.w < a.Co);
+  const int slot = wk.x, p0 = wk.y, p1 = wk.z, o0 = wk.w;
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int j4 = lane >> 4, i16 = lane & 15;
+  const int mh = wave & 1, ph = wave >> 1;    // channel half, pixel half
+  const int Ci = a.Ci, Co = a.Co;
+  for (int i = tid; i < 2 * TC; i += 256) (&acc_lds[0][0])[i] = 0;
+  // ---- this thread's chunks of the pixel tile: q = tid + 256 j -> (pixel q / 4, 4 channels), constant over the k chunks
+  const float* xrow = a.x + (long)p0 * Ci;
+  int xo[BQ];
+  unsigned okx = 0;
+#pragma unroll
+  for (int j = 0; j < BQ; ++j) {
+    const int q = tid + 256 * j;
+    xo[j] = (q >> 2) * Ci + 4 * (q & 3);
+    okx |= (unsigned)(p0 + (q >> 2) < p1) << j;
+  }
+  // ---- and of the weight tile: forward (r, k4): W[o0 + r][k0 + 4 k4 ..]; data gradient (r4, k): W[k0 + k][o0 + 4 r4 ..]
+  // (the 4 rows of one k: transposed by the store)
+  const float* wrow = a.w + (long)slot * a.w_mstride + a.w_off;
+  int wo[AQ];
+  unsigned okw = 0;
+#pragma unroll
+  for (int j = 0; j < AQ; ++j) {
+    const int q = tid + 256 * j;
+    if constexpr (!DGRAD) {
+      wo[j] = (o0 + (q >> 2)) * Ci + 4 * (q & 3);
+      okw |= (unsigned)(o0 + (q >> 2) < Co) << j;
+    } else {
+      wo[j] = (q & 15) * Co + o0 + 4 * (q >> 4);
+      okw |= (unsigned)(o0 + 4 * (q >> 4) < Co) << j;
+    }
+  }
+  float4 rx[BQ], rw[AQ];
+  auto load = [&](int kc) __attribute__((always_inline)) {
+#pragma unroll
+    for (int j = 0; j < BQ; ++j)
+      rx[j] = ((okx >> j) & 1u) ? *reinterpret_cast<const float4*>(xrow + xo[j] + BKC * kc)
+                                : make_float4(0.f, 0.f, 0.f, 0.f);
+    const int wk0 = DGRAD ? BKC * kc * Co : BKC * kc;
+#pragma unroll
+    for (int j = 0; j < AQ; ++j)
+      rw[j] = ((okw >> j) & 1u) ? *reinterpret_cast<const float4*>(wrow + wo[j] + wk0)
+                                : make_float4(0.f, 0.f, 0.f, 0.f);
+  };
+  auto store = [&]() __attribute__((always_inline)) {
+#pragma unroll
+    for (int j = 0; j < BQ; ++j) {
+      const int q = tid + 256 * j;
+      *reinterpret_cast<float4*>(xL + (q >> 2) * P + 4 * (q & 3)) = rx[j];
+    }
+#pragma unroll
+    for (int j = 0; j < AQ; ++j) {
+      const int q = tid + 256 * j;
+      if constexpr (!DGRAD) {
+        *reinterpret_cast<float4*>(wL + (q >> 2) * P + 4 * (q & 3)) = rw[j];
+      } else {
+        float* d = wL + 4 * (q >> 4) * P + (q & 15);
+        d[0] = rw[j].x, d[P] = rw[j].y, d[2 * P] = rw[j].z, d[3 * P] = rw[j].w;
+      }
+    }
+  };
+  f32x4_t acc[MT][NT];
+#pragma unroll
+  for (int m = 0; m < MT; ++m)
+#pragma unroll
+    for (int n = 0; n < NT; ++n) acc[m][n] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+  const float* wt0 = wL + ((TC / 2) * mh + i16) * P + 4 * j4;
+  const float* xt0 = xL + ((TP / 2) * ph + i16) * P + 4 * j4;
+  const int nc = Ci / BKC;
+  load(0);
+  for (int kc = 0; kc < nc; ++kc) {
+    t3_barrier();  // the previous chunk's tiles are consumed (first chunk: acc_lds zeroed)
+    store();
+    t3_barrier();
+    if (kc + 1 < nc) load(kc + 1);  // the next chunk's loads stay in flight under this chunk's MFMAs
+    float4 av[MT], bv[NT];
+#pragma unroll
+    for (int m = 0; m < MT; ++m) av[m] = *reinterpret_cast<const float4*>(wt0 + 16 * m * P);
+#pragma unroll
+    for (int n = 0; n < NT; ++n) bv[n] = *reinterpret_cast<const float4*>(xt0 + 16 * n * P);
+#pragma unroll
+    for (int q = 0; q < 4; ++q)  // (k group outermost: 16 independent accumulators between two MFMAs on the same one)
+#pragma unroll
+      for (int m = 0; m < MT; ++m)
+#pragma unroll
+        for (int n = 0; n < NT; ++n) {
+          const float ae = q == 0 ? av[m].x : (q == 1 ? av[m].y : (q == 2 ? av[m].z : av[m].w));
+          const float be = q == 0 ? bv[n].x : (q == 1 ? bv[n].y : (q == 2 ? bv[n].z : bv[n].w));
+          acc[m][n] = mfma4(ae, be, acc[m][n]);
+        }
+  }
+  // ---- epilogue: lane holds channels o0 + (TC / 2) mh + 16 m + 4 j4 + i of pixel p0 + (TP / 2) ph + 16 n + i16
+  float ss[MT][4], sq[MT][4];
+#pragma unroll
+  for (int m = 0; m < MT; ++m)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) ss[m][i] = sq[m][i] = 0.f;
+#pragma unroll
+  for (int n = 0; n < NT; ++n) {
+    const int p = p0 + (TP / 2) * ph + 16 * n + i16;
+#pragma unroll
+    for (int m = 0; m < MT; ++m) {
+      const int co = o0 + (TC / 2) * mh + 16 * m + 4 * j4;
+      f32_epi4<EPI>(a, slot, p, co, p < p1 && co < Co, acc[m][n], ss[m], sq[m]);
+    }
+  }
+  if constexpr (EPI & 4)
+    f32_stats_flush<TC, (EPI & 2) ? DTF_FX_GRAD : DTF_FX_STAT>(a, slot, o0, ss, sq, acc_lds, MT * mh);
 }
 
 // ------------------------------------------------------------------------------------------------------ wgrad
@@ -1493,6 +1640,36 @@ DTF_API int dtf_f32_conv_t3(const F32Args* a, int tc, int epi, int dgrad, int w,
   T3_WS(4, false) T3_WS(5, false) T3_WS(6, true) T3_WS(7, true)
 #undef T3_WS
 #undef T3_CASE
+  return -1;
+}
+
+// pointwise fwd / dgrad of a stride-1 1x1 conv (f32conv_pw_kernel), operand as stored (MODE 0): work rows (slot, p0, p1,
+// o0) of up to dtf_f32_conv_pw_tp(tc) consecutive pixels of one member x tc output channels, tc one of
+// dtf_f32_conv_pw_tc(0 ..) (0 ends the list); Ci, Co multiples of 16; epi 0 / 4 / 5 (forward: plain, statistics
+// [+ residual]) or 0 / 3 / 6 / 7 (data gradient: plain, residual + mask, mask + BN-backward sums [+ residual]).
+DTF_API int dtf_f32_conv_pw_tc(int i) { return i >= 0 && i < PW_NTC ? pw_tc(i) : 0; }
+DTF_API int dtf_f32_conv_pw_tp(int tc) { return pw_tp(tc); }
+
+DTF_API int dtf_f32_conv_pw(const F32Args* a, int tc, int epi, int dgrad, int nwork, hipStream_t stream) {
+  if (nwork <= 0) return 0;
+  if (a->kh != 1 || a->kw != 1 || a->stride != 1 || a->pad != 0 || a->Hi != a->Ho || a->Wi != a->Wo || a->Ci <= 0 ||
+      a->Ci % 16 != 0 || a->Co <= 0 || a->Co % 16 != 0 || a->wci != a->Ci || a->wrows != 0 || (a->w_off & 3) != 0 ||
+      (a->w_mstride & 3) != 0)
+    return -2;
+  DTF_HOST_CHECK(DTF_ALIGNED16(a->x) && DTF_ALIGNED16(a->y) && DTF_ALIGNED16(a->w) && a->work);
+  DTF_HOST_CHECK(!(epi & 1) || DTF_ALIGNED16(a->res));
+  DTF_HOST_CHECK(!(epi & 2) || (DTF_ALIGNED16(a->xm) && a->c_ep));
+  DTF_HOST_CHECK(!(epi & 4) || a->st_out);
+#define PW_CASE(TC_, E_, D_)                                                                                   \
+  if (tc == TC_ && epi == E_ && dgrad == D_) {                                                                 \
+    hipLaunchKernelGGL((f32conv_pw_kernel<TC_, pw_tp(TC_), E_, D_>), dim3(nwork), dim3(256), 0, stream, *a);   \
+    return DTF_CHECK_LAUNCH();                                                                                 \
+  }
+#define PW_TCS(E_, D_) PW_CASE(128, E_, D_) PW_CASE(64, E_, D_)
+  PW_TCS(0, false) PW_TCS(4, false) PW_TCS(5, false)
+  PW_TCS(0, true) PW_TCS(3, true) PW_TCS(6, true) PW_TCS(7, true)
+#undef PW_TCS
+#undef PW_CASE
   return -1;
 }
 

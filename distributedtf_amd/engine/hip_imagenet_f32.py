@@ -16,6 +16,9 @@ accumulation in fp32, by overriding the plan's kernel vocabulary:
   stride-1 1x1       every plan: forward and data gradient on f32conv_pw_kernel (a GEMM over flat pixel ranges of one
                      member, 128 x 128 or, for outputs of at most 64 channels, 64 x 256 tiles) unless ``_F32_PW`` is off;
                      data gradients with a reduction below ``_F32_PW_DGRAD_MIN_K`` channels keep the generic kernel
+  stride-2 dgrad     every plan: the data gradients of the 3x3 / 2 convs and 1x1 / 2 projections on f32dgrad_s2_kernel
+                     (one dense GEMM per output-parity class over the dy grid, 1 / 2 / 2 / 4 taps) unless ``_F32_DS2``
+                     is off
   dense layer        the same kernels as a 1x1 conv over the GAP features, the class dimension padded to 1024
                      (F32Args.wrows keeps the padding off the 1001-row weight matrix)
   BN apply / sums    f32conv.hip f32_ew (relu(BN), BN-backward apply, v1 relu(BN + shortcut)), f32_bwd_sums
@@ -58,6 +61,12 @@ _F32_PW_EPI = {False: (0, 4, 5), True: (0, 3, 6, 7)}  # the instantiated epilogu
 # at 64 and 128 the pointwise kernel measured 6 - 17 % slower per launch there (267 vs 230, 758 vs 655, 1114 vs 960,
 # 479 vs 451 us), from 256 up 6 - 33 % faster; every forward class is faster (profiles/f32_pw_ab.txt)
 _F32_PW_DGRAD_MIN_K = 256
+# data gradients of the 1x1 / 2 and 3x3 / 2 convs (plain operand) by output-parity class on f32dgrad_s2_kernel;
+# DTF_F32_DS2=0 runs the generic kernel there (the launch lists of before the kernel existed).
+_F32_DS2 = os.environ.get("DTF_F32_DS2", "1") == "1"
+_F32_DS2_EPI = (0, 6, 7)  # the instantiated epilogues
+# parity classes (py * 2 + px of the dx pixel), heaviest first: 4, 2, 2, 1 taps at 3x3; at 1x1 only class 0 has a tap
+_F32_DS2_CLASSES = {3: (3, 1, 2, 0), 1: (0, 1, 2, 3)}
 
 _REGISTERED = False
 
@@ -82,6 +91,9 @@ def _register():
     ops.register("dtf_f32_conv_pw", [P(F32Args), c_int, c_int, c_int, c_int, c_void_p])
     ops.register("dtf_f32_conv_pw_tc", [c_int])
     ops.register("dtf_f32_conv_pw_tp", [c_int])
+    ops.register("dtf_f32_dgrad_s2", [P(F32Args), c_int, c_int, c_int, c_void_p])
+    ops.register("dtf_f32_dgrad_s2_tc", [c_int])
+    ops.register("dtf_f32_dgrad_s2_tp", [c_int])
     ops.register("dtf_f32_wgrad_t3", [P(F32Args), c_int, c_int, c_void_p])
     ops.register("dtf_f32_wgrad_t3_rows", [c_int])
     for q in ("pack", "to", "ti"):
@@ -212,7 +224,25 @@ class _ImageNetF32Plan(_ImageNetPlan):
                 and epi in _F32_PW_EPI[bool(dgrad)] and (not dgrad or a.Ci >= _F32_PW_DGRAD_MIN_K)):
             self._pw_launch(a, src, out, epi, dgrad)
             return
+        if (_F32_DS2 and dgrad and c.stride == 2 and c.k in (1, 3) and mode == 0 and not stem and a.Ci % 16 == 0
+                and a.Co % 16 == 0 and epi in _F32_DS2_EPI):
+            self._ds2_launch(a, src, out, epi)
+            return
         self._conv_launch(a, src, out, mode, epi, dgrad)
+
+    def _ds2_launch(self, a, src, out, epi):
+        """Data gradient of a 1x1 / 2 or 3x3 / 2 conv on f32dgrad_s2_kernel: ``_pix_work`` items (slot, q0, q1,
+        o0 | class << 16) of flat class-pixel ranges over the dy grid x the kernel's channel tile, every parity class of
+        every member, the classes with the most taps first."""
+        L = ops.lib()
+        hw2 = a.Hi * a.Wi
+        assert src.numel() == self.N * hw2 * a.Ci and out.numel() == 4 * self.N * hw2 * a.Co
+        a.x, a.y = _p(src), _p(out)
+        tc = L.dtf_f32_dgrad_s2_tc(0)
+        work = self._pix_work(a.Hi, a.Co, tc, classes=_F32_DS2_CLASSES[a.kh], tp=L.dtf_f32_dgrad_s2_tp(tc))
+        a.work = _p(work)
+        self._hold(a)
+        self._add(L.dtf_f32_dgrad_s2, ctypes.byref(a), tc, epi, work.shape[0])
 
     def _pw_launch(self, a, src, out, epi, dgrad):
         """Stride-1 1x1 forward / data gradient on f32conv_pw_kernel: items (slot, p0, p1, o0) of flat pixel ranges of

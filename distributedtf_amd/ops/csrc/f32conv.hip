@@ -15,6 +15,8 @@
 //             shared bn_final kernel (convg_aux.hip) turns into coefficients.
 //  f32conv_band / f32conv_t3 : the stride-1 3x3 case from LDS-resident row bands (CIFAR widths, all channels resident;
 //             ImageNet widths, the reduction walked in 16-channel chunks).
+//  f32conv_pw / f32dgrad_s2 : GEMMs over flat pixel ranges: the stride-1 1x1 conv and its data gradient; the data
+//             gradient of a 1x1 / 2 or 3x3 / 2 conv, one dense GEMM per parity class of the dx pixels.
 //  f32wgrad : dW[o][k] += sum_p T_dy(dy)[p][o] * T_x(gather(x))[p][k], split over pixel chunks, fp32 atomics into
 //             the member's gradient row.
 //  f32wgrad_band / f32wgrad_t3 : the stride-1 3x3 weight gradient from LDS-resident row bands (CIFAR widths, all
@@ -804,6 +806,162 @@ __global__ __launch_bounds__(256, 2) DTF_F32_NO_PK void f32conv_pw_kernel(F32Arg
     for (int m = 0; m < MT; ++m) {
       const int co = o0 + (TC / 2) * mh + 16 * m + 4 * j4;
       f32_epi4<EPI>(a, slot, p, co, p < p1 && co < Co, acc[m][n], ss[m], sq[m]);
+    }
+  }
+  if constexpr (EPI & 4)
+    f32_stats_flush<TC, (EPI & 2) ? DTF_FX_GRAD : DTF_FX_STAT>(a, slot, o0, ss, sq, acc_lds, MT * mh);
+}
+
+// ------------------------------------------------------------------------- stride-2 data gradient by parity class
+// Data gradient of a k x k / 2 conv, k in {1, 3}, forward padding (k - 1) / 2, dx grid = 2 x the dy grid.  The dx
+// pixels fall into four classes by parity, class = py * 2 + px for dx pixel (2 cy + py, 2 cx + px), and inside one
+// class the transposed convolution is a dense GEMM over the dy grid with a fixed tap list: along an axis, parity 0 has
+// the one tap k = 1 at dy offset 0, parity 1 the taps k = 2 at offset 0 and k = 0 at offset +1 (zero beyond the bottom /
+// right edge) -- 1, 2, 2 or 4 taps per class where the gather kernel stages and multiplies all 9 for every pixel; for
+// k = 1 class 0 has its one tap and classes 1 - 3 have none: they run the epilogue on zero accumulators (dx must still
+// be written, and with a residual or statistics it is not zero).
+// Work item (slot, q0, q1, o0 | class << 16): up to DS2_TP class pixels q = (image * Hi + cy) * Wi + cx of one member
+// (a flat range that ignores image boundaries, ragged tail allowed) times DS2_TC dx channels from o0 (the last channel
+// tile may be partial).  q is also the dy pixel index of the offset-0 taps, so staging needs (cy, cx) only for the two
+// edge predicates; q -> (image, cy, cx) is divided out once per item for the thread's 2 staged pixels and, after the
+// reduction, for its 4 epilogue pixels (the dx address) -- the k loop has no division.
+// The tile is f32conv_pw_kernel's data-gradient form: 128 x 128, waves 2 (channel halves) x 2 (pixel halves), 16
+// accumulator tiles each; the reduction walks (tap, 16-channel chunk), dy staged [pixel][k] with float4 loads and
+// stores, W[o][tap][i0 ..] (contiguous along the dx channels) transposed to [row][k] by the store, row pitch 24 floats,
+// both read back as ds_read_b128 with the band kernels' k-permutation; the next chunk's global loads stay in registers
+// under the current chunk's 64 MFMAs per wave.  Rows past Co, pixels past q1 and taps beyond the edge are staged as
+// zeros, so every LDS word an MFMA reads has been written; they store and count nothing.
+constexpr int DS2_TC = 128, DS2_TP = 128;
+
+template <int EPI>
+__global__ __launch_bounds__(256, 2) DTF_F32_NO_PK void f32dgrad_s2_kernel(F32Args a) {
+  constexpr int TC = DS2_TC, TP = DS2_TP, BKC = PW_BKC, P = BKC + 8;
+  constexpr int MT = TC / 32, NT = TP / 32;   // 16 x 16 tiles per wave: rows (dx channels), columns (class pixels)
+  constexpr int AQ = TC * (BKC / 4) / 256, BQ = TP * (BKC / 4) / 256;  // float4 chunks per thread and stage
+  static_assert(MT * NT == 16 && AQ >= 1 && BQ >= 1 && TC % 64 == 0 && TP % 64 == 0, "ds2 geometry");
+  static_assert(2 * ((TC + TP) * P * 4 + 2 * TC * 8) <= 65536, "ds2 LDS: two workgroups in 64 KB");
+  __shared__ __attribute__((aligned(16))) float wL[TC * P];
+  __shared__ __attribute__((aligned(16))) float xL[TP * P];
+  __shared__ dtf_acc_t acc_lds[2][TC];
+  const int4 wk = a.work[blockIdx.x];
+  DTF_WG_CHECK(wk.x >= 0 && wk.y >= 0 && wk.z > wk.y && wk.z - wk.y <= TP && wk.w >= 0 && (wk.w >> 16) < 4 &&
+               (wk.w & 0xffff) % 16 == 0 && (wk.w & 0xffff) < a.Co);
+  const int slot = wk.x, q0 = wk.y, q1 = wk.z, o0 = wk.w & 0xffff;
+  const int py = (wk.w >> 17) & 1, px = (wk.w >> 16) & 1;
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int j4 = lane >> 4, i16 = lane & 15;
+  const int mh = wave & 1, ph = wave >> 1;    // channel half, pixel half
+  const int Ci = a.Ci, Co = a.Co, Wi = a.Wi, HWi = a.Hi * a.Wi;
+  const bool k3 = a.kh == 3;
+  const int kk = a.kh * a.kw;
+  // ---- the class's taps: t = ty * ntx + tx, dy offset (ty, tx), kernel index ky = 1 (parity 0) | 2, 0 (parity 1)
+  const int ntx = k3 ? 1 + px : 1;
+  const int ntap = k3 ? (1 + py) * ntx : (py | px ? 0 : 1);
+  for (int i = tid; i < 2 * TC; i += 256) (&acc_lds[0][0])[i] = 0;
+  // ---- this thread's chunks of the pixel tile: q = tid + 256 j -> (class pixel q / 4, 4 channels); bit j of okx: the
+  // pixel is inside the item, of oky / okc: it has a dy row below / a dy column to its right
+  long xo[BQ];
+  unsigned okx = 0, oky = 0, okc = 0;
+#pragma unroll
+  for (int j = 0; j < BQ; ++j) {
+    const int q = tid + 256 * j;
+    const bool ok = q0 + (q >> 2) < q1;
+    const int qq = ok ? q0 + (q >> 2) : q0;
+    const int rem = qq - (qq / HWi) * HWi, cy = rem / Wi, cx = rem - cy * Wi;
+    xo[j] = (long)qq * Ci + 4 * (q & 3);
+    okx |= (unsigned)ok << j;
+    oky |= (unsigned)(ok && cy + 1 < a.Hi) << j;
+    okc |= (unsigned)(ok && cx + 1 < Wi) << j;
+  }
+  // ---- and of the weight tile (r4, k): W[k0 + k][tap][o0 + 4 r4 ..] (the 4 rows of one k: transposed by the store)
+  const float* wrow = a.w + (long)slot * a.w_mstride + a.w_off;
+  int wo[AQ];
+  unsigned okw = 0;
+#pragma unroll
+  for (int j = 0; j < AQ; ++j) {
+    const int q = tid + 256 * j;
+    wo[j] = (q & 15) * kk * Co + o0 + 4 * (q >> 4);
+    okw |= (unsigned)(o0 + 4 * (q >> 4) < Co) << j;
+  }
+  float4 rx[BQ], rw[AQ];
+  auto load = [&](int t, int kc) __attribute__((always_inline)) {
+    const int tx = ntx == 2 ? t & 1 : 0, ty = ntx == 2 ? t >> 1 : t;
+    const int ky = !k3 ? 0 : (py ? (ty ? 0 : 2) : 1), kx = !k3 ? 0 : (px ? (tx ? 0 : 2) : 1);
+    const unsigned ok = okx & (ty ? oky : ~0u) & (tx ? okc : ~0u);
+    const int xk0 = (ty * Wi + tx) * Ci + BKC * kc;
+#pragma unroll
+    for (int j = 0; j < BQ; ++j)
+      rx[j] = ((ok >> j) & 1u) ? *reinterpret_cast<const float4*>(a.x + xo[j] + xk0)
+                               : make_float4(0.f, 0.f, 0.f, 0.f);
+    const int wk0 = (BKC * kc * kk + ky * a.kw + kx) * Co;
+#pragma unroll
+    for (int j = 0; j < AQ; ++j)
+      rw[j] = ((okw >> j) & 1u) ? *reinterpret_cast<const float4*>(wrow + wo[j] + wk0)
+                                : make_float4(0.f, 0.f, 0.f, 0.f);
+  };
+  auto store = [&]() __attribute__((always_inline)) {
+#pragma unroll
+    for (int j = 0; j < BQ; ++j) {
+      const int q = tid + 256 * j;
+      *reinterpret_cast<float4*>(xL + (q >> 2) * P + 4 * (q & 3)) = rx[j];
+    }
+#pragma unroll
+    for (int j = 0; j < AQ; ++j) {
+      const int q = tid + 256 * j;
+      float* d = wL + 4 * (q >> 4) * P + (q & 15);
+      d[0] = rw[j].x, d[P] = rw[j].y, d[2 * P] = rw[j].z, d[3 * P] = rw[j].w;
+    }
+  };
+  f32x4_t acc[MT][NT];
+#pragma unroll
+  for (int m = 0; m < MT; ++m)
+#pragma unroll
+    for (int n = 0; n < NT; ++n) acc[m][n] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+  const float* wt0 = wL + ((TC / 2) * mh + i16) * P + 4 * j4;
+  const float* xt0 = xL + ((TP / 2) * ph + i16) * P + 4 * j4;
+  const int nc = Ci / BKC, nit = ntap * nc;
+  if (nit == 0) t3_barrier();  // (a tapless class: acc_lds zeroed before the statistics)
+  else load(0, 0);
+  for (int it = 0, t = 0, kc = 0; it < nit; ++it) {
+    t3_barrier();  // the previous chunk's tiles are consumed (first chunk: acc_lds zeroed)
+    store();
+    t3_barrier();
+    if (++kc == nc) kc = 0, ++t;
+    if (it + 1 < nit) load(t, kc);  // the next chunk's loads stay in flight under this chunk's MFMAs
+    float4 av[MT], bv[NT];
+#pragma unroll
+    for (int m = 0; m < MT; ++m) av[m] = *reinterpret_cast<const float4*>(wt0 + 16 * m * P);
+#pragma unroll
+    for (int n = 0; n < NT; ++n) bv[n] = *reinterpret_cast<const float4*>(xt0 + 16 * n * P);
+#pragma unroll
+    for (int q = 0; q < 4; ++q)  // (k group outermost: 16 independent accumulators between two MFMAs on the same one)
+#pragma unroll
+      for (int m = 0; m < MT; ++m)
+#pragma unroll
+        for (int n = 0; n < NT; ++n) {
+          const float ae = q == 0 ? av[m].x : (q == 1 ? av[m].y : (q == 2 ? av[m].z : av[m].w));
+          const float be = q == 0 ? bv[n].x : (q == 1 ? bv[n].y : (q == 2 ? bv[n].z : bv[n].w));
+          acc[m][n] = mfma4(ae, be, acc[m][n]);
+        }
+  }
+  // ---- epilogue: lane holds channels o0 + (TC / 2) mh + 16 m + 4 j4 + i of class pixel q0 + (TP / 2) ph + 16 n + i16,
+  // which is dx pixel (image, 2 cy + py, 2 cx + px)
+  float ss[MT][4], sq[MT][4];
+#pragma unroll
+  for (int m = 0; m < MT; ++m)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) ss[m][i] = sq[m][i] = 0.f;
+#pragma unroll
+  for (int n = 0; n < NT; ++n) {
+    const int q = q0 + (TP / 2) * ph + 16 * n + i16;
+    const bool ok = q < q1;
+    const int qq = ok ? q : q0;
+    const int img = qq / HWi, rem = qq - img * HWi, cy = rem / Wi, cx = rem - cy * Wi;
+    const long p = ((long)img * a.Ho + 2 * cy + py) * a.Wo + 2 * cx + px;
+#pragma unroll
+    for (int m = 0; m < MT; ++m) {
+      const int co = o0 + (TC / 2) * mh + 16 * m + 4 * j4;
+      f32_epi4<EPI>(a, slot, p, co, ok && co < Co, acc[m][n], ss[m], sq[m]);
     }
   }
   if constexpr (EPI & 4)
@@ -1670,6 +1828,36 @@ DTF_API int dtf_f32_conv_pw(const F32Args* a, int tc, int epi, int dgrad, int nw
   PW_TCS(0, true) PW_TCS(3, true) PW_TCS(6, true) PW_TCS(7, true)
 #undef PW_TCS
 #undef PW_CASE
+  return -1;
+}
+
+// data gradient of a k x k / 2 conv, k in 1 / 3, forward padding (k - 1) / 2 (f32dgrad_s2_kernel), operand as stored
+// (MODE 0): x = dy on the Hi x Wi grid with Ci channels, y = dx on the 2 Hi x 2 Wi grid with Co channels; work rows
+// (slot, q0, q1, o0 | class << 16) of up to dtf_f32_dgrad_s2_tp(tc) consecutive class pixels of one member x tc dx
+// channels, class = py * 2 + px the parity of the dx pixel, tc one of dtf_f32_dgrad_s2_tc(0 ..) (0 ends the list); every
+// class of every member must be listed (each writes its own quarter of dx); Ci, Co multiples of 16; epi 0 / 6 / 7
+// (plain, mask + BN-backward sums [+ residual]).
+DTF_API int dtf_f32_dgrad_s2_tc(int i) { return i == 0 ? DS2_TC : 0; }
+DTF_API int dtf_f32_dgrad_s2_tp(int tc) { return tc == DS2_TC ? DS2_TP : 0; }
+
+DTF_API int dtf_f32_dgrad_s2(const F32Args* a, int tc, int epi, int nwork, hipStream_t stream) {
+  if (nwork <= 0) return 0;
+  if (a->kh != a->kw || (a->kh != 1 && a->kh != 3) || a->stride != 2 || a->pad != (a->kh - 1) / 2 || a->Hi <= 0 ||
+      a->Wi <= 0 || a->Ho != 2 * a->Hi || a->Wo != 2 * a->Wi || a->Ci <= 0 || a->Ci % 16 != 0 || a->Co <= 0 ||
+      a->Co % 16 != 0 || a->Co > 65535 || a->wci != a->Ci || a->wrows != 0 || (a->w_off & 3) != 0 ||
+      (a->w_mstride & 3) != 0)
+    return -2;
+  DTF_HOST_CHECK(DTF_ALIGNED16(a->x) && DTF_ALIGNED16(a->y) && DTF_ALIGNED16(a->w) && a->work);
+  DTF_HOST_CHECK(!(epi & 1) || DTF_ALIGNED16(a->res));
+  DTF_HOST_CHECK(!(epi & 2) || (DTF_ALIGNED16(a->xm) && a->c_ep));
+  DTF_HOST_CHECK(!(epi & 4) || a->st_out);
+#define DS2_CASE(E_)                                                                                     \
+  if (tc == DS2_TC && epi == E_) {                                                                       \
+    hipLaunchKernelGGL((f32dgrad_s2_kernel<E_>), dim3(nwork), dim3(256), 0, stream, *a);                 \
+    return DTF_CHECK_LAUNCH();                                                                           \
+  }
+  DS2_CASE(0) DS2_CASE(6) DS2_CASE(7)
+#undef DS2_CASE
   return -1;
 }
 
